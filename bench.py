@@ -1,13 +1,22 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X sampling hot path: sampled structures / second for a T-step predictor-corrector run.
 
-    python bench.py --gpus N --steps K --warmup W [--workload C2|C3|C4|C5]
+    python bench.py --gpus N --steps K --warmup W [--workload C2|C3|C4|C5] [--full] [--dump-outputs DIR]
     (N > 1: launched by torch.distributed.run, one rank per GPU, RCCL)
 
 A "step" is one sampler iteration -- score-network forward + fused predictor update, then M x (forward + fused
 corrector update) -- over one batch of synthetic structures resident in HBM.  K steps are timed between
 barrier + synchronize pairs, the MAX over ranks is taken, and the whole-job throughput is derived for the
 workload's full trajectory:  value = structures / (T * ms_per_step + gather_ms).
+
+A plain run does only that: set up, W warm-up steps, the K timed steps, the job's one collective, the JSON line
+(for the MLP workloads also the whole-trajectory launch their `value` comes from, see below).
+`--full` adds everything else the bench measures: one whole T-iteration trajectory timed end to end (EGNN workloads,
+where it fits --whole-job-budget-s; `value` then comes from it), the other arithmetic mode of the edge chain, the MLP
+kernel families, the roofline launches below, the card's power / clock sensor, the other BASELINE configurations
+(`also_measured`) and the CPU baseline.  `--dump-outputs DIR` writes the composition the K timed steps ended with
+(A, X, L as DIR/<name>.npy, float32); the inputs are seeded, so equal arguments give equal inputs.
+
 Workloads: C3 = BASELINE configs[2] (Si 2x2x2, EGNN 4x256 with the radius graph, T=1000, M=2,
 B=512 per GPU) is the default -- the largest single-GPU configuration and the one north_star's target is quoted on;
 C2 = configs[1] (Si 1x1x1, MLP); C4/C5 are the other EGNN configurations.  Weak scaling: every rank samples its own
@@ -19,7 +28,7 @@ touched the GPU -- runs `python -m torch.distributed.run --nproc-per-node N benc
 its output and exits with its code.  For the MLP workloads the job is a single 4 ms launch, so `value` comes from a
 timed region that is one whole T-iteration trajectory whatever --steps says (`ms_per_step` is still the K-step figure).
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline      the dominant hand-written kernel of the workload: algorithmic bytes per launch / average launch
                 duration measured here with HIP events on the stream the kernel runs on, against 8 TB/s;
   cpu_baseline  the CPU oracle (oracle/, a restatement of the reference pinned to its golden vectors; kind "port")
@@ -691,11 +700,24 @@ class Job:
         return elapsed, local
 
 
+def dump_outputs(folder, composition, rank):
+    """What a caller of the timed path receives after its last step -- the composition A (atom types, exact in float32), X
+    (relative coordinates), L (lattice parameters) -- as folder/<name>.npy in float32; ranks other than 0 prefix `rank<r>_`.
+    The inputs are seeded (network weights NET_SEED, Philox BASE_SEED + rank), so equal arguments give equal inputs."""
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    prefix = "" if rank == 0 else f"rank{rank}_"
+    for field, tensor in zip(("A", "X", "L"), composition):
+        np.save(os.path.join(folder, f"{prefix}{field}.npy"), tensor.detach().cpu().numpy().astype(np.float32))
+
+
 def measure_workload(job, name, steps, warmup, whole_job_budget_s, egnn_precision, resampling_arg=None, batch_arg=None,
-                     no_graph=False, forward_arg=None, other_mode=True, families=True, sensor=None):
+                     no_graph=False, forward_arg=None, other_mode=True, families=True, measure_roofline=True, sensor=None,
+                     dump_dir=None):
     """One workload on this process's card: the K-step region, the whole-job region where it fits the budget, the job's one
-    collective, the dominant kernels' launch durations.  Returns the pieces of a JSON line (every rank runs it; rank 0 alone
-    times the stand-alone kernel launches)."""
+    collective, the dominant kernels' launch durations (`measure_roofline`).  Returns the pieces of a JSON line (every rank runs
+    it; rank 0 alone times the stand-alone kernel launches).  With `dump_dir`, the composition the K-step region ended with is
+    written there (dump_outputs)."""
     args, device, dist, world, rank = job.args, job.device, job.dist, job.world, job.rank
     w = WORKLOADS[name]
     batch = batch_arg or w["batch"]
@@ -728,6 +750,8 @@ def measure_workload(job, name, steps, warmup, whole_job_budget_s, egnn_precisio
             sensor.start()
         elapsed, local = timed(lambda: advance(loop, steps, T))
         ms_per_step, ms_per_step_local = elapsed * 1e3 / steps, local * 1e3 / steps
+        if dump_dir is not None:
+            dump_outputs(dump_dir, loop.composition, rank)
         # MLP workloads: the product runs the whole trajectory as ONE launch (4 ms); K iterations of it pay the launch's
         # fixed cost once per K.  So the job time is measured directly: one whole T-iteration trajectory, timed the same way.
         trajectory_ms = trajectory_ms_local = None
@@ -803,7 +827,7 @@ def measure_workload(job, name, steps, warmup, whole_job_budget_s, egnn_precisio
                                                    value=round((batch * world) / ((generic["padded_family"] + gather_ms) * 1e-3), 2)))
 
         roofline = forward_gemm = None
-        if rank == 0:
+        if rank == 0 and measure_roofline:
             if forward == "fused":
                 m = time_fused_kernel(gen, loop, batch, w, device)
             elif w["dominant"] == "pc_step_kernel":
@@ -886,8 +910,9 @@ def as_line(m, world, egnn_precision, backend):
                    "env": {k: v for k, v in sorted(os.environ.items()) if k.startswith("MDX_")},
                    "peak_device_memory_bytes": m["peak_memory"],
                    "f16_range_fallbacks": m["f16_range_fallbacks"]},
-        "roofline": m["roofline"],
     }
+    if m["roofline"] is not None:
+        line["roofline"] = m["roofline"]
     if m["generic_path"] is not None:
         line["generic_path"] = m["generic_path"]
     if m["other_mode"] is not None:
@@ -900,10 +925,10 @@ def as_line(m, world, egnn_precision, backend):
     return line
 
 
-# The other BASELINE configurations, measured after the primary workload on the same card when the bench is run with its
-# defaults at N = 1: (workload, steps, warmup, resampling, whole-job budget in seconds).  C2's job is one 4 ms launch and is
-# timed whole, with its three kernel families; C4 is a 20-iteration region (its whole job is C3's, 31 s); C5 a 3-iteration
-# region without and with the resampling pass (its whole jobs take 6 and 11 minutes: profiles/r04_bench_c5_whole_job.json).
+# The other BASELINE configurations, measured after the primary workload on the same card when the bench is run with --full
+# and otherwise its defaults at N = 1: (workload, steps, warmup, resampling, whole-job budget in seconds).  C2's job is one
+# 4 ms launch and is timed whole, with its three kernel families; C4 is a 20-iteration region (its whole job is C3's, 31 s);
+# C5 a 3-iteration region without and with the resampling pass (its whole jobs take 6 and 11 minutes: profiles/r04_bench_c5_whole_job.json).
 ALSO_MEASURED = (("C2", None, None, None, 0.0), ("C4", 20, 2, None, 0.0), ("C5", 3, 1, 0, 0.0), ("C5", 3, 1, 1, 0.0))
 
 
@@ -918,11 +943,19 @@ def main():
     ap.add_argument("--forward", choices=["fused", "pytorch"], default=None,
                     help="score-network forward: 'pytorch' (plugin API, any network) or 'fused' (MLP only: network "
                          "forward + update in one persistent HIP kernel); default: fused for MLP workloads")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: the whole-trajectory timing (default budget "
+                         "150 s), the other edge-chain mode, the MLP kernel families, the roofline launches, the card's "
+                         "sensor, the other BASELINE configurations (--also-measured auto) and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the composition they computed (A, X, L of the last step) as "
+                         "DIR/<name>.npy in float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--whole-job-budget-s", type=float, default=150.0,
+    ap.add_argument("--whole-job-budget-s", type=float, default=None,
                     help="EGNN workloads: after the K-step region, time ONE WHOLE T-iteration trajectory (graph replays + the "
                          "status read) and report `value` from it, when T x ms_per_step is below this many seconds "
-                         "(C3 / C4: ~31 s; C5's 2000 x 0.17 .. 0.34 s is not, its value stays T x ms_per_step); 0 = never")
+                         "(C3 / C4: ~31 s; C5's 2000 x 0.17 .. 0.34 s is not, its value stays T x ms_per_step); 0 = never; "
+                         "default 150 with --full, 0 without")
     ap.add_argument("--resampling", type=int, default=None,
                     help="C5 only: RePaint resampling passes per time index (BASELINE configs[4] 'with resampling'; "
                          "default 1; 0 = the reference's loop, which has no resampling)")
@@ -933,12 +966,13 @@ def main():
                     help="EGNN workloads: arithmetic of the fused per-edge MFMA kernel -- 'f16x3' (the product's default) "
                          "split-f16 three-product form with binary32 accumulation, binary32-level accuracy (error against fp64 "
                          "equal to the f32 paths': tests/test_egnn_chain_gpu.py); 'f32' exact binary32 MFMA; 'library' = "
-                         "per-layer PyTorch modules (no hand-written chain).  The other MFMA mode is timed too and reported beside it.")
+                         "per-layer PyTorch modules (no hand-written chain).  With --full the other MFMA mode is timed too "
+                         "and reported beside it.")
     ap.add_argument("--master-port", type=int, default=None,
                     help="rendezvous port when bench.py starts its own ranks (default: a free port of 127.0.0.1)")
     ap.add_argument("--also-measured", choices=["auto", "yes", "no"], default="auto",
                     help="after the primary workload, measure the other BASELINE configurations (ALSO_MEASURED) on the same card "
-                         "and report them under `also_measured`; auto = at N = 1 with the default workload")
+                         "and report them under `also_measured`; auto = with --full, at N = 1 with the default workload")
     ap.add_argument("--rehearse-launch", action="store_true",
                     help="no GPU work: the ranks only run the job's control flow on host tensors (gloo) -- rendezvous, the "
                          "packed all-gather of synthetic compositions, the MAX reduction, the per-rank record, rank 0's JSON "
@@ -982,19 +1016,21 @@ def run_rank(args, w, world, rank):
                 dist.barrier()
     assert args.gpus == world, f"--gpus {args.gpus} but WORLD_SIZE={world}"
     job = Job(args, device, dist, world, rank)
-    sensor = CardSensor(device.index)
+    sensor = CardSensor(device.index) if args.full else None
+    whole_job_budget = args.whole_job_budget_s if args.whole_job_budget_s is not None else (150.0 if args.full else 0.0)
 
-    m = measure_workload(job, args.workload, args.steps, args.warmup, args.whole_job_budget_s, args.egnn_precision,
+    m = measure_workload(job, args.workload, args.steps, args.warmup, whole_job_budget, args.egnn_precision,
                          resampling_arg=args.resampling, batch_arg=args.batch, no_graph=args.no_graph,
-                         forward_arg=args.forward, sensor=sensor)
+                         forward_arg=args.forward, other_mode=args.full, families=args.full, measure_roofline=args.full,
+                         sensor=sensor, dump_dir=args.dump_outputs)
     # the per-rank record: ONE small all-gather after the timed regions
     nan = float("nan")
     record = (rank, m["ms_per_step_local"], m["trajectory_ms_local"] if m["trajectory_ms_local"] is not None else nan,
-              *sensor.summary(), m["f16_range_fallbacks"])
+              *(sensor.summary() if sensor is not None else (nan, nan, nan, 0.0)), m["f16_range_fallbacks"])
     per_rank = gather_per_rank(dist, world, record, device=device if args.backend == "nccl" else None)
 
     also = None
-    wanted = args.also_measured == "yes" or (args.also_measured == "auto" and world == 1 and args.workload == "C3"
+    wanted = args.also_measured == "yes" or (args.also_measured == "auto" and args.full and world == 1 and args.workload == "C3"
                                              and args.batch is None and args.forward is None and not args.no_graph)
     if wanted:
         also = []
@@ -1002,7 +1038,7 @@ def run_rank(args, w, world, rank):
             t0 = time.perf_counter()
             try:
                 other = measure_workload(job, name, steps, warmup, budget, args.egnn_precision, resampling_arg=resampling,
-                                         other_mode=False, families=True)
+                                         other_mode=False, families=True, measure_roofline=True)
                 entry = as_line(other, world, args.egnn_precision, args.backend if dist is not None else None)
             except Exception as exc:          # noqa: BLE001  (a side measurement must not take the primary line with it: say so)
                 if world > 1:
@@ -1023,7 +1059,7 @@ def run_rank(args, w, world, rank):
     result["per_rank"], result["slowest_rank"], result["n1_equivalent"] = per_rank, slowest, n1
     if also is not None:
         result["also_measured"] = also
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             result["cpu_baseline"] = cpu_baseline(w, args.workload, resampling=m["resampling"])
         except Exception as exc:              # noqa: BLE001  (the measured line is printed whatever the CPU leg does: say what it did)

@@ -560,14 +560,14 @@ def test_compute_distances_in_batch_against_golden(cuda):
 
 @pytest.mark.parametrize("workload", [None, "C2"])
 def test_bench_contract(cuda, workload):
-    """bench.py prints ONE JSON line with the contract's keys: the default workload (C3 = the headline configuration) and
-    C2, whose `value` comes from one whole trajectory timed end to end whatever --steps says."""
+    """bench.py --full prints ONE JSON line with the contract's keys: the default workload (C3 = the headline configuration)
+    and C2, whose `value` comes from one whole trajectory timed end to end whatever --steps says."""
     import json
     import subprocess
     import sys as _sys
     from conftest import ROOT
     steps, warmup = (2, 1) if workload is None else (20, 5)
-    cmd = [_sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup),
+    cmd = [_sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", str(steps), "--warmup", str(warmup),
            "--no-cpu-baseline"] + ([] if workload is None else ["--workload", workload])
     env = dict({k: v for k, v in os.environ.items() if not k.startswith("MDX_")}, MDX_STRAY_VARIABLE="1")   # (MDX_FUZZ is the tests')
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
@@ -608,6 +608,35 @@ def test_bench_contract(cuda, workload):
         hbm = d["roofline_hbm"]
         assert hbm["kernel"].startswith("mdx_egnn_radius_graph") and hbm["launches_per_build"] == 2
         assert hbm["avg_launch_us"] < hbm["count_scan_fill_form_us"] and hbm["traffic"] >= hbm["algorithmic_bytes_per_launch"]
+
+
+def test_bench_plain_run_and_its_outputs(cuda, tmp_path):
+    """A plain bench.py run (no --full): the headline line alone -- value from K steps x T + gather, none of the side
+    measurements -- and --dump-outputs writes the composition the timed steps ended with, in float32."""
+    import json
+    import subprocess
+    import sys as _sys
+    import numpy as np
+    from conftest import ROOT
+    cmd = [_sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert d["unit"] == "structures/s" and d["metric"].startswith("sampled structures/sec") and d["dtype"].startswith("f32")
+    assert d["value_from"] == "total_time_steps x ms_per_step + gather"
+    assert abs(d["value"] - d["config"]["global_batch"] / ((1000 * d["ms_per_step"] + d["config"]["gather_ms"]) * 1e-3)) \
+        < 1e-3 * d["value"]
+    for key in ("roofline", "roofline_hbm", "other_edge_chain_mode", "also_measured", "cpu_baseline", "generic_path"):
+        assert key not in d, key
+    dumped = {name: np.load(tmp_path / "out" / f"{name}.npy") for name in ("A", "X", "L")}
+    assert all(a.dtype == np.float32 for a in dumped.values())
+    assert dumped["A"].shape == (512, 64) and dumped["X"].shape == (512, 64, 3) and dumped["L"].shape == (512, 6)
+    assert np.all(np.isfinite(dumped["X"])) and np.all((dumped["X"] >= 0) & (dumped["X"] <= 1))
+    assert set(np.unique(dumped["A"])) <= {0.0, 1.0}
 
 
 def test_updates_with_device_scalars_equal_host_scalars(cuda):

@@ -33,7 +33,7 @@ def test_bench_distributed_branch_on_one_gpu(cuda):
     """bench.py exactly as the driver launches it for N > 1, with N = 1: rank 0's JSON line reports one GPU, a gather that took
     time on the device (the job's one collective really ran), and bench.py itself asserts that the gathered block equals the
     rank's local composition."""
-    run = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "C2", "--steps", "50", "--warmup", "5",
+    run = _torchrun([os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--workload", "C2", "--steps", "50", "--warmup", "5",
                      "--no-cpu-baseline"], port=29571)
     assert run.returncode == 0, run.stderr[-4000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]
