@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(CSRC, "libmdx_hip.so")
 MDX_OK = 0
 MDX_PREDICTOR, MDX_CORRECTOR = 0, 1
 STATUS_CUTOFF_TOO_LARGE, STATUS_MASK_AT_LAST_STEP, STATUS_EGNN_F16_RANGE, STATUS_GRAPH_CAPACITY = 1, 2, 4, 8
+STATUS_EGNN_TABLE = 16
 EGNN_COORD_NORMALIZE, EGNN_COORD_TANH = 1, 2      # MDX_EGNN_COORD_* (coord_flags of mdx_egnn_node_gather / _coord_aggregate)
 EGNN_CHAIN_MAX_LAYERS = 16
 MAX_CLASSES = 8
@@ -33,7 +34,7 @@ ABI_SYMBOLS = (
     "mdx_mlp_pc_sample", "mdx_mlp_pc_sample_variant", "mdx_mlp_pc_sample_workspace_floats", "mdx_mlp_image_floats", "mdx_mlp_pack_image", "mdx_egnn_message_input", "mdx_egnn_coord_head", "mdx_segment_rows",
     "mdx_egnn_chain_image_bytes", "mdx_egnn_chain_pack", "mdx_egnn_chain_adapt_activation_exponents", "mdx_egnn_edge_chain", "mdx_egnn_piece_rows", "mdx_segment_combine", "mdx_egnn_node_gather", "mdx_mlp_chain_rows", "mdx_egnn_coord_aggregate",
     "mdx_egnn_node_inputs", "mdx_egnn_scores", "mdx_egnn_outputs", "mdx_node_mlp_rows", "mdx_node_mlp_rows_split",
-    "mdx_rng_fill", "mdx_math_probe",
+    "mdx_egnn_table_check", "mdx_egnn_table_gather", "mdx_rng_fill", "mdx_math_probe",
 )
 MLP_MAX_HIDDEN = 8
 # options of mdx_mlp_pc_sample (include/mdx_hip.h)
@@ -210,6 +211,10 @@ def _declare(L):
     L.mdx_segment_combine.argtypes = [vp, i64, vp, vp, i64, i32, i32, vp, vp, vp]
     L.mdx_egnn_node_gather.restype = i32
     L.mdx_egnn_node_gather.argtypes = [vp, i64, vp, vp, i64, i32, i32, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp]
+    L.mdx_egnn_table_check.restype = i32
+    L.mdx_egnn_table_check.argtypes = [vp, vp, i32, i32, i32, vp, i64, f32, vp, vp, vp, vp]
+    L.mdx_egnn_table_gather.restype = i32
+    L.mdx_egnn_table_gather.argtypes = [vp, vp, i32, i32, i32, f32, vp, vp, vp, i64, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp]
     L.mdx_egnn_chain_adapt_activation_exponents.restype = i32
     L.mdx_egnn_chain_adapt_activation_exponents.argtypes = [vp, i32, vp, vp]
     L.mdx_egnn_piece_rows.restype = i64

@@ -25,7 +25,8 @@ from typing import Optional
 import torch
 
 from .. import kernels
-from .._hip import MDX_CORRECTOR, MDX_PREDICTOR, STATUS_MASK_AT_LAST_STEP, MdxError, PcFlags, Rng
+from .._hip import (MDX_CORRECTOR, MDX_PREDICTOR, STATUS_EGNN_F16_RANGE, STATUS_EGNN_TABLE, STATUS_MASK_AT_LAST_STEP,
+                    MdxError, PcFlags, Rng)
 from ..models.score_networks.score_network import ScoreNetwork
 from ..namespace import AXL, CARTESIAN_FORCES, NOISE, NOISY_AXL_COMPOSITION, TIME
 from ..noise_schedulers.noise_parameters import NoiseParameters
@@ -80,6 +81,7 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
         # ITERATIONS recomputed with the exact-f32 MFMA kernels because the split-f16 ones met a value beyond the f16 range
         # (_guarded_iteration, IterationLoop._advance_watched); logged by sample_diffusion, printed by bench.py
         self.f16_range_fallbacks = 0
+        self.table_fallbacks = 0         # MDX_STATUS_EGNN_TABLE reports (the network's first layer left the distance table)
         self.resampling_steps = 0     # set by ConstrainedLangevinGenerator (repaint_resampling_steps)
         self._visit = 0               # which of the 1 + resampling_steps passes through the current time index
 
@@ -298,7 +300,15 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
         if not isinstance(sigma_noise, torch.Tensor) or sigma_noise.dim() == 0:
             sigma_noise = torch.full((composition.X.shape[0], 1), float(sigma_noise), dtype=torch.float32, device=composition.X.device)
         batch = {NOISY_AXL_COMPOSITION: composition, TIME: time, NOISE: sigma_noise, CARTESIAN_FORCES: cartesian_forces}
-        return self.axl_network(batch, conditional=False)
+        net = self.axl_network
+        if not hasattr(net, "sigma_uniform_hint"):
+            return net(batch, conditional=False)
+        # (the loop fills one sigma for the whole batch: the network may run its first graph layer on a distance grid)
+        net.sigma_uniform_hint = True
+        try:
+            return net(batch, conditional=False)
+        finally:
+            net.sigma_uniform_hint = False
 
     # ---------------------------------------------------------------------------------------------------------
     # one step = network forward + ONE fused update kernel
@@ -441,22 +451,48 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
     # ---------------------------------------------------------------------------------------------------------
     SPLIT_F16_MODES = ("f16x3", "f16x3_32x32")
 
-    def _range_guarded(self) -> bool:
-        """Does the score network run split-f16 kernels that can report a value beyond the f16 range?"""
-        return getattr(self.axl_network, "edge_chain_precision", None) in self.SPLIT_F16_MODES
+    REPORTS = STATUS_EGNN_F16_RANGE | STATUS_EGNN_TABLE
 
-    def _take_range_report(self) -> bool:
-        """Read the network's status word (a host synchronisation) and clear the f16-range bit; other bits stay for
-        check_status()."""
-        from .._hip import STATUS_EGNN_F16_RANGE
+    def _range_guarded(self) -> bool:
+        """Does the score network run split-f16 kernels that can report a value beyond the f16 range, or a first-layer
+        distance table that can report MDX_STATUS_EGNN_TABLE?"""
+        net = self.axl_network
+        return getattr(net, "edge_chain_precision", None) in self.SPLIT_F16_MODES or \
+            getattr(net, "first_layer_table", "off") != "off"
+
+    def _take_range_report(self) -> int:
+        """Read the network's status word (a host synchronisation) and clear its f16-range and table bits: the ones of those
+        that were set (other bits stay for check_status())."""
         status = getattr(self.axl_network, "graph_status", None)
         if status is None:
-            return False
-        word = int(status.item())
-        if word & STATUS_EGNN_F16_RANGE:
-            status.bitwise_and_(~STATUS_EGNN_F16_RANGE)
-            return True
-        return False
+            return 0
+        word = int(status.item()) & self.REPORTS
+        if word:
+            status.bitwise_and_(~self.REPORTS)
+        return word
+
+    def _count_table_fallback(self, index_i: int):
+        """MDX_STATUS_EGNN_TABLE: the network's first layer goes back to the per-edge chain for the rest of the process."""
+        import warnings
+        self.table_fallbacks += 1
+        self.axl_network.first_layer_table = "off"
+        warnings.warn(f"EGNN first layer: the distance table failed its check at time index {index_i}; this iteration is "
+                      "recomputed on the per-edge chain, and the network's first_layer_table is now 'off'")
+
+    def _recompute(self, report: int, run):
+        """run() with what a report asks for: the exact-f32 kernels for this call (f16 range), the per-edge first layer from
+        now on (table)."""
+        net = self.axl_network
+        if not report & STATUS_EGNN_F16_RANGE:
+            return run()
+        precision = net.edge_chain_precision
+        self._begin_f16_fallback()
+        net.edge_chain_precision = "f32"
+        try:
+            return run()
+        finally:
+            net.edge_chain_precision = precision
+            self._adapt_f16_range()
 
     def _adapt_f16_range(self):
         """After the exact-f32 pass: the network derives per-layer activation exponents for its split-f16 kernels from the
@@ -476,10 +512,9 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
     def _clear_stale_range_report(self):
         """A range bit left in the network's word by something that was not an iteration of this loop (the warm-up iterations
         before a capture, a caller stepping by hand) must not be read as the first iteration's report."""
-        from .._hip import STATUS_EGNN_F16_RANGE
         status = getattr(self.axl_network, "graph_status", None)
         if status is not None and self._range_guarded():
-            status.bitwise_and_(~STATUS_EGNN_F16_RANGE)
+            status.bitwise_and_(~self.REPORTS)
 
     def _count_fallback(self, index_i: int):
         import warnings
@@ -515,9 +550,13 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
         marks = self._recorder_marks() if self.record else None
         try:
             out = self._iteration(composition, i, forces)
-            if not self._take_range_report():
+            report = self._take_range_report()
+            if not report:
                 return out
-            self._count_fallback(i)
+            if report & STATUS_EGNN_F16_RANGE:
+                self._count_fallback(i)
+            if report & STATUS_EGNN_TABLE:
+                self._count_table_fallback(i)
             if marks is not None:
                 self._recorder_truncate(marks)
             if keeps:
@@ -526,14 +565,7 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
             # what the dropped attempt raised in the generator's own word goes with it (non-finite logits at time index 0 leave
             # MASKs behind: MDX_STATUS_MASK_AT_LAST_STEP) -- the exact-f32 pass raises it again if it is real
             self._status.bitwise_and_(~STATUS_MASK_AT_LAST_STEP)
-            precision = net.edge_chain_precision
-            self._begin_f16_fallback()
-            net.edge_chain_precision = "f32"
-            try:
-                return self._iteration(composition, i, forces)
-            finally:
-                net.edge_chain_precision = precision
-                self._adapt_f16_range()
+            return self._recompute(report, lambda: self._iteration(composition, i, forces))
         finally:
             if keeps:
                 self.noise_source = source
@@ -639,7 +671,8 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
                     self.use_fixed_lattice_parameters, self.small_epsilon, self.num_classes)     # kernel arguments of the capture
         words = tuple(None if w is None else w.data_ptr() for w in (self._call_word, self._status))   # read by the captured kernels
         return (tuple(start.X.shape), tuple(start.L.shape), str(start.X.device), getattr(net, "edge_chain_precision", None),
-                settings, words, tuple((p.data_ptr(), p._version) for p in net.parameters()))
+                getattr(net, "first_layer_table", None), settings, words,
+                tuple((p.data_ptr(), p._version) for p in net.parameters()))
 
     def _sample_with_graph(self, start: AXL, starting_step_index: int, ending_step_index: int) -> AXL:
         """The iteration is captured ONCE per (shape, network state) and kept: later sample() calls copy their starting
@@ -798,7 +831,6 @@ class IterationLoop:
         return self._watch
 
     def _advance_watched(self, iterations: int):
-        from .._hip import STATUS_EGNN_F16_RANGE
         gen, w = self.generator, self._watch_buffers()
         net, slots = gen.axl_network, self.LAG + 1
         gen._clear_stale_range_report()                 # (nothing of this call is queued yet: a set bit is someone else's)
@@ -821,7 +853,8 @@ class IterationLoop:
                 continue
             slot = checked % slots
             w["events"][slot].synchronize()
-            if not int(w["words"][slot]) & STATUS_EGNN_F16_RANGE:
+            report = int(w["words"][slot]) & gen.REPORTS
+            if not report:
                 checked += 1
                 continue
             # iteration `checked` left the f16 range: everything queued behind it worked on its output -- drop it
@@ -830,16 +863,16 @@ class IterationLoop:
                 dst.copy_(src)
             self.remaining = first - checked
             kernels.index_set(self.d_index, self.remaining - 1)
-            status.bitwise_and_(~STATUS_EGNN_F16_RANGE)
+            status.bitwise_and_(~gen.REPORTS)
             gen._status.zero_()                         # (bits the dropped iterations may have raised)
-            gen._count_fallback(self.remaining - 1)
-            precision = net.edge_chain_precision
-            gen._begin_f16_fallback()
-            net.edge_chain_precision = "f32"
-            try:
-                self._one(visits=1 + gen.resampling_steps)      # eager launches of the same iteration, exact-f32 kernels
-            finally:
-                net.edge_chain_precision = precision
-                gen._adapt_f16_range()
+            if report & STATUS_EGNN_F16_RANGE:
+                gen._count_fallback(self.remaining - 1)
+            if report & STATUS_EGNN_TABLE:
+                gen._count_table_fallback(self.remaining - 1)
+                # the captured iteration runs the table: from here on this loop launches eagerly (a later sample() call
+                # captures again -- first_layer_table is part of the graph's key)
+                self.graph = None
+            # eager launches of the same iteration (exact-f32 kernels after an f16-range report)
+            gen._recompute(report, lambda: self._one(visits=1 + gen.resampling_steps))
             checked += 1
             k = checked

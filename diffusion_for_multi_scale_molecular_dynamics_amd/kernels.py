@@ -944,6 +944,84 @@ def egnn_node_gather(pieces, n_edges: int, offsets, degree, mean_messages: bool,
     return out, coord_out
 
 
+# ---- the first graph layer on a distance grid (mdx_egnn_table_check / _gather)
+TABLE_INV_SPACING = 256.0        # h = 2^-8 between the even grid points: rho_k = k h / 2, k^2 < 2^24 keeps rho_k^2 exact
+# largest midpoint error, relative to the class pair's largest |value|: the chain's own rounding noise sits at ~2e-6 of that
+# (exact-f32 and split-f16 alike, measured at C3 / C4 -- csrc/mdx_egnn_table.hip), so the check is set 8x above it; an
+# interpolation error that passes it is below the network's binary32 noise floor in the scores
+TABLE_TOLERANCE = 2.0 ** -16
+
+
+@dataclass
+class EgnnTable:
+    """What the first graph layer needs to run on the grid: the grid problem's per-node projections [G, 2H] (the class
+    embeddings at the batch's sigma through the layer's first weight), sigma [B] (checked to be uniform on the device), the
+    nodes' classes [n_nodes] int64 (MASK = n_classes - 1) and the grid's size."""
+    grid_proj: torch.Tensor
+    sigma: torch.Tensor
+    atom_types: torch.Tensor
+    n_classes: int
+    n_even: int
+
+
+def egnn_table_points(coord_dimension: int) -> int:
+    """Even grid points for the torus uplift of coord_dimension = 2 n_k components: rho <= 2 sqrt(n_k), and the cubic of the
+    cell [m h, (m+1) h) reads points m - 1 .. m + 2."""
+    import math
+    return int(math.ceil(math.sqrt(2.0 * coord_dimension) * TABLE_INV_SPACING)) + 3
+
+
+_TABLE_GRIDS = {}
+
+
+def egnn_table_grid(n_classes: int, n_even: int, coord_dimension: int, device):
+    """The grid problem (fixed for a shape, built once per device): node classes [G] int64, coordinates [G, D] and the sorted
+    edge list [n_classes^2 K, 2].  Node a < n_classes is the source of class a at the origin; node n_classes + b K + r the
+    destination of class b at (rho_r, 0, ..., 0), rho_r = r h for r < n_even and (r - n_even + 1/2) h after that; edge row
+    p K + r, p = a n_classes + b, joins a to (b, r): the row layout of mdx_egnn_table_check."""
+    key = (n_classes, n_even, coord_dimension, str(device))
+    if key not in _TABLE_GRIDS:
+        K = 2 * n_even - 1
+        r = torch.arange(K, dtype=torch.float64)
+        rho = torch.where(r < n_even, r, r - n_even + 0.5) / TABLE_INV_SPACING
+        classes = torch.cat([torch.arange(n_classes), torch.arange(n_classes).repeat_interleave(K)])
+        coord = torch.zeros(n_classes * (K + 1), coord_dimension, dtype=F32)
+        coord[n_classes:, 0] = rho.to(F32).repeat(n_classes)
+        a = torch.arange(n_classes).repeat_interleave(n_classes * K)
+        dst = n_classes + torch.arange(n_classes * K).repeat(n_classes)
+        edges = torch.stack([a, dst], dim=1)
+        _TABLE_GRIDS[key] = (classes.to(device), coord.to(device), edges.contiguous().to(device))
+    return _TABLE_GRIDS[key]
+
+
+def egnn_table_check(table, table_scalar, n_classes: int, n_even: int, sigma, workspace, worst=None, status=None):
+    """Midpoint check of the grid table (mdx_egnn_table_check): MDX_STATUS_EGNN_TABLE into `status` on failure."""
+    H = table.shape[1]
+    assert table.shape[0] == n_classes * n_classes * (2 * n_even - 1) and workspace.numel() >= n_classes ** 2 * (H + 2)
+    rc = lib().mdx_egnn_table_check(ptr(table, F32, "table"), ptr(table_scalar, F32, "table_scalar"), H, n_classes, n_even,
+                                    ptr(sigma, F32, "sigma"), sigma.numel(), TABLE_TOLERANCE, ptr(workspace, I32, "workspace"),
+                                    ptr(worst, F32, "worst"), ptr(status, I32, "status"), stream_handle())
+    check(rc, "mdx_egnn_table_check")
+
+
+def egnn_table_gather(table, table_scalar, n_classes: int, n_even: int, atom_types, offsets, degree, mean_messages: bool, left,
+                      coord, edges, mean_coords: bool, flags: int = 0, status=None):
+    """egnn_node_gather's outputs with the messages and scalars interpolated from the grid table (mdx_egnn_table_gather)."""
+    n_nodes, H = degree.shape[0], table.shape[1]
+    assert left is None or tuple(left.shape) == (n_nodes, H)
+    assert atom_types.shape[0] == n_nodes and table.shape[0] == n_classes * n_classes * (2 * n_even - 1)
+    out = torch.empty(n_nodes, H if left is None else 2 * H, dtype=F32, device=table.device)
+    coord_out = torch.empty_like(coord)
+    rc = lib().mdx_egnn_table_gather(ptr(table, F32, "table"), ptr(table_scalar, F32, "table_scalar"), H, n_classes, n_even,
+                                     TABLE_INV_SPACING, ptr(atom_types, I64, "atom_types"), ptr(offsets, I64, "offsets"),
+                                     ptr(degree, I64, "degree"), n_nodes, int(bool(mean_messages)), ptr(left, F32, "left"),
+                                     ptr(out, F32, "out"), ptr(coord, F32, "coord"), coord.shape[1], ptr(edges, I64, "edges"),
+                                     int(bool(mean_coords)), int(flags), ptr(coord_out, F32, "coord_out"),
+                                     ptr(status, I32, "status"), stream_handle())
+    check(rc, "mdx_egnn_table_gather")
+    return out, coord_out
+
+
 def egnn_node_inputs(x, k_vectors, sigma, atom_types, emb_weight, emb_bias, second=None):
     """z [n_nodes, 2 n_k] (torus uplift) and h [n_nodes, H] (embedding of [sigma | one_hot]) of EGNNScoreNetwork, one launch.
     x [B, N, 3] relative coordinates, sigma [B] (or [B,1]), atom_types [B, N] int64.

@@ -108,6 +108,8 @@ class E_GCL(nn.Module):
         state.pop("_node_mlp_kept", None)
         state.pop("_node_chain_kept", None)
         state.pop("_activation_scales", None)
+        state.pop("_table_workspace", None)
+        state.pop("table_worst", None)
         return state
 
     def _scales(self, kind: str, n_layers: int, device):
@@ -322,13 +324,16 @@ class E_GCL(nn.Module):
     def forward(self, h: torch.Tensor, edge_index: torch.Tensor, coord: torch.Tensor,
                 degree: Optional[torch.Tensor] = None, offsets: Optional[torch.Tensor] = None,
                 n_edges: Optional[torch.Tensor] = None, node_proj: Optional[torch.Tensor] = None,
-                next_layer: Optional["E_GCL"] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                next_layer: Optional["E_GCL"] = None, table=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """node_proj: this layer's per-node projections [n_nodes, 2H], when the previous layer's node kernel has already
         computed them; next_layer: the graph layer that follows (its projections are then computed by this layer's node
         kernel and left in self._next_proj).
         h [n_nodes, F]; edge_index [E, 2] sorted by column 0; coord [n_nodes, D]; degree [n_nodes] edge counts;
         offsets [n_nodes] = exclusive scan of degree (enables the segment kernels on device tensors); n_edges: int64 [1]
-        on the device when edge_index is a capacity-sized list whose first n_edges rows are the edges (fused chain only)."""
+        on the device when edge_index is a capacity-sized list whose first n_edges rows are the edges (fused chain only);
+        table: kernels.EgnnTable when the caller guarantees what the layer's per-edge output on a distance grid needs (one
+        value of h per class, the coordinates a torus uplift): the edge chain then runs on the grid and the edges are
+        interpolated from it (_table_gather)."""
         row, col = edge_index[:, 0], edge_index[:, 1]
         if degree is None:
             degree = torch.bincount(row, minlength=h.shape[0])
@@ -339,7 +344,8 @@ class E_GCL(nn.Module):
         if fused and offsets is not None and edge_index.shape[0] > 0:
             pack = self._edge_chain_pack()
             if pack is not None:
-                return self._forward_edge_chain(pack, h, edge_index, coord, degree, offsets, n_edges, node_proj, next_layer)
+                return self._forward_edge_chain(pack, h, edge_index, coord, degree, offsets, n_edges, node_proj, next_layer,
+                                                table)
         assert n_edges is None, "a capacity-sized edge list needs the fused edge chain in every layer"
         count = degree.clamp(min=1).to(h.dtype).unsqueeze(1)      # (the reference DIVIDES by the count: egnn_utils.py:66-68)
 
@@ -373,12 +379,44 @@ class E_GCL(nn.Module):
         return out, coord
 
 
-    def _forward_edge_chain(self, pack, h, edge_index, coord, degree, offsets, n_edges=None, node_proj=None, next_layer=None):
-        """E_GCL.forward with the per-edge work in one MFMA kernel: node projections (library GEMM, per node) -> fused
-        chain -> the two sorted-segment reductions -> node MLP."""
+    def table_applies(self, pack, h, coord) -> bool:
+        """Can the layer run on the distance grid (_table_gather)?  The chain's ROWS mode has no attention gate; the gather
+        has the output contract of the node gather (full-width messages, H <= 256, D <= 8) and reports to the status word."""
+        return (pack is not None and not self.attention and pack.piece_sums_ok and pack.message_width == pack.hidden
+                and pack.hidden <= 256 and h.shape[1] == pack.hidden and coord.shape[1] <= 8 and self.status_word is not None
+                and h.shape[0] < (1 << 31))
+
+    def _table_gather(self, pack, table, left, coord, edge_index, offsets, degree):
+        """egnn_node_gather's ([left | message sums] or the sums, coord_out) with the per-edge chain replaced by the chain on the
+        distance grid (kernels.egnn_table_grid), its midpoint check (MDX_STATUS_EGNN_TABLE into the status word when it fails
+        or sigma is not uniform) and the interpolating gather.  Fixed sizes, no host read: capture-safe."""
         from .. import kernels
-        proj = node_proj if node_proj is not None else torch.nn.functional.linear(h, pack.proj_weight)
+        _, grid_coord, grid_edges = kernels.egnn_table_grid(table.n_classes, table.n_even, coord.shape[1], coord.device)
+        values, scalars = kernels.egnn_edge_chain(pack, table.grid_proj, grid_coord, grid_edges, status=self.status_word)
+        key = (table.n_classes, pack.hidden, str(coord.device))
+        if getattr(self, "_table_workspace", (None,))[0] != key:
+            # (zero-filled once; every check leaves it zeroed)
+            self._table_workspace = (key, torch.zeros(table.n_classes ** 2 * (pack.hidden + 2), dtype=torch.int32,
+                                                      device=coord.device))
+            self.table_worst = torch.zeros(1, dtype=torch.float32, device=coord.device)
+        kernels.egnn_table_check(values, scalars, table.n_classes, table.n_even, table.sigma, self._table_workspace[1],
+                                 worst=self.table_worst, status=self.status_word)
+        return kernels.egnn_table_gather(values, scalars, table.n_classes, table.n_even, table.atom_types, offsets, degree,
+                                         self.message_mean, left, coord, edge_index, self.coords_mean,
+                                         flags=self._coord_flags(), status=self.status_word)
+
+    def _forward_edge_chain(self, pack, h, edge_index, coord, degree, offsets, n_edges=None, node_proj=None, next_layer=None,
+                            table=None):
+        """E_GCL.forward with the per-edge work in one MFMA kernel: node projections (library GEMM, per node) -> fused
+        chain -> the two sorted-segment reductions -> node MLP.  With `table` (and table_applies) the per-edge chain and the
+        node gather are _table_gather."""
+        from .. import kernels
         coord = coord.contiguous()
+        if table is not None and self.table_applies(pack, h, coord):
+            def gather(left):
+                return self._table_gather(pack, table, left, coord, edge_index, offsets, degree)
+            return self._node_part(h, gather, next_layer)
+        proj = node_proj if node_proj is not None else torch.nn.functional.linear(h, pack.proj_weight)
         # the messages are added up per node inside the kernel (piece sums) and never written out as [E, H]
         in_kernel = pack.piece_sums_ok and h.shape[0] < (1 << 31)
         messages, edge_scalar = kernels.egnn_edge_chain(pack, proj.contiguous(), coord, edge_index, status=self.status_word,
@@ -392,29 +430,39 @@ class E_GCL(nn.Module):
                    else kernels.segment_rows(messages, offsets, degree, self.message_mean))
             node_in = torch.cat([h, agg[:, :pack.message_width]], dim=1)
         elif in_kernel and h.shape[1] == messages.shape[1] and coord.shape[1] <= 8:
-            whole = self._node_mlp_pack(next_layer)
-            if whole is not None and whole.hidden == h.shape[1]:
-                # everything per node between the edge chain and the node MLP in one pass (the message sums and the updated
-                # coordinates), then the whole node MLP (its 2H -> H layer included, reading h and the sums as the two halves of
-                # its input row: [h | agg] is never formed), the residual and -- when a graph layer follows -- that layer's
-                # per-node projections: one launch on the matrix cores
-                h = h.contiguous()
-                agg, coord_out = kernels.egnn_node_gather(messages, edge_index.shape[0], offsets, degree, self.message_mean,
-                                                          None, edge_scalar, coord, edge_index, self.coords_mean,
-                                                          flags=self._coord_flags())
-                out = kernels.node_mlp_rows(whole, h, self.residual, status=self.status_word, agg=agg)
-                if whole.projects:
-                    out, self._next_proj = out
-                return out, coord_out
-            node_in, coord_out = kernels.egnn_node_gather(messages, edge_index.shape[0], offsets, degree, self.message_mean,
-                                                          h.contiguous(), edge_scalar, coord, edge_index, self.coords_mean,
-                                                          flags=self._coord_flags())
+            def gather(left):
+                return kernels.egnn_node_gather(messages, edge_index.shape[0], offsets, degree, self.message_mean, left,
+                                                edge_scalar, coord, edge_index, self.coords_mean, flags=self._coord_flags())
+            return self._node_part(h, gather, next_layer)
         else:
             coord_out = kernels.egnn_coord_aggregate(edge_scalar, coord, edge_index, offsets, degree, self.coords_mean,
                                                      flags=self._coord_flags())
             agg = (kernels.segment_combine(messages, edge_index.shape[0], offsets, degree, self.message_mean) if in_kernel
                    else kernels.segment_rows(messages, offsets, degree, self.message_mean))
             node_in = torch.cat([h, agg], dim=1)
+        return self._node_mlp_tail(h, node_in, coord_out)
+
+    def _node_part(self, h, gather, next_layer):
+        """Everything per node after the per-edge work, from gather(left) -> ([left | message sums] or the sums, coord_out)."""
+        from .. import kernels
+        whole = self._node_mlp_pack(next_layer)
+        if whole is not None and whole.hidden == h.shape[1]:
+            # everything per node between the edge chain and the node MLP in one pass (the message sums and the updated
+            # coordinates), then the whole node MLP (its 2H -> H layer included, reading h and the sums as the two halves of
+            # its input row: [h | agg] is never formed), the residual and -- when a graph layer follows -- that layer's
+            # per-node projections: one launch on the matrix cores
+            h = h.contiguous()
+            agg, coord_out = gather(None)
+            out = kernels.node_mlp_rows(whole, h, self.residual, status=self.status_word, agg=agg)
+            if whole.projects:
+                out, self._next_proj = out
+            return out, coord_out
+        node_in, coord_out = gather(h.contiguous())
+        return self._node_mlp_tail(h, node_in, coord_out)
+
+    def _node_mlp_tail(self, h, node_in, coord_out):
+        """The node MLP on node_in = [h | agg] and the residual."""
+        from .. import kernels
         node_pack = self._node_chain_pack()
         if node_pack is not None and (not self.residual or h.shape[1] == node_pack.hidden):
             # first node layer (2H -> H, + SiLU): a PyTorch matmul per node; the other layers and the residual: one MFMA launch
@@ -456,12 +504,13 @@ class EGNN(nn.Module):
                 message_agg=message_agg, tanh=tanh))
 
     def forward(self, h: torch.Tensor, edges: torch.Tensor, x: torch.Tensor, degree=None, embedded: bool = False,
-                first_proj: Optional[torch.Tensor] = None, classify: bool = True) -> AXL:
+                first_proj: Optional[torch.Tensor] = None, classify: bool = True, first_table=None) -> AXL:
         """degree: None (a caller's own edge list, any order), the edge count per node [n_nodes] of a list sorted by source,
         or the triple (degree, offsets, n_edges) of a capacity-sized list (utils/neighbors.get_edges_static).
         embedded: h is already embedding_in(node features) (kernels.egnn_node_inputs); first_proj: the first graph layer's
         per-node projections [n_nodes, 2H] of that h, when the caller has them.  classify=False: A is the last layer's h (the
-        caller applies node_classification_layer: kernels.egnn_outputs) and L is None."""
+        caller applies node_classification_layer: kernels.egnn_outputs) and L is None.  first_table: kernels.EgnnTable for the
+        first graph layer (E_GCL.forward's `table`)."""
         emb = self.embedding_in
         if embedded:
             assert h.shape[1] == emb.out_features
@@ -487,7 +536,8 @@ class EGNN(nn.Module):
         proj = first_proj
         for k, layer in enumerate(self.graph_layers):
             following = self.graph_layers[k + 1] if k + 1 < len(self.graph_layers) else None
-            h, x = layer(h, edges, x, degree, offsets, n_edges, node_proj=proj, next_layer=following)
+            h, x = layer(h, edges, x, degree, offsets, n_edges, node_proj=proj, next_layer=following,
+                         table=first_table if k == 0 else None)
             proj = layer.__dict__.pop("_next_proj", None)       # left there by the layer's node kernel, if it computed them
         if not classify:
             return AXL(A=h, X=x, L=None)

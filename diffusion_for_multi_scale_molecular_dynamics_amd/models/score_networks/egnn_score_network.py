@@ -118,12 +118,20 @@ class EGNNScoreNetwork(ScoreNetwork):
         # logged.  Applies when every graph layer runs the fused edge chain (nothing else then needs E on the host).
         self.static_edge_list_max_fraction = 0.5
         self._logged_two_call_switch = False
+        # The first graph layer on a distance grid (models/egnn.py E_GCL._table_gather): "on" whenever
+        # the layer's shape allows it (the device checks that sigma is uniform and raises MDX_STATUS_EGNN_TABLE otherwise),
+        # "off" never, "auto" in a sampler's forwards (the generator fills sigma itself and says so through
+        # sigma_uniform_hint) when the grid has at most an eighth of the edge list's rows.  A generator that reads
+        # MDX_STATUS_EGNN_TABLE recomputes that iteration on the per-edge chain and sets "off".
+        self.first_layer_table = "auto"
+        self.sigma_uniform_hint = False
         self.egnn = self._make_egnn(hp)
 
     def __getstate__(self):
         """Copies and pickles of the module carry no cached device tensors (the fully connected edge lists)."""
         state = dict(self.__dict__)
         state.pop("_fully_connected_edges", None)
+        state.pop("_table_grid_x", None)
         return state
 
     @property
@@ -190,6 +198,35 @@ class EGNNScoreNetwork(ScoreNetwork):
                 b2 = (pack.proj_weight.double() @ emb.bias.double()).float().contiguous()
             self._first_projection = (stamp, (w2, b2))
         return self._first_projection[1]
+
+    def _first_layer_table(self, edges, z, h, sigma, atom_types, k_vectors, second):
+        """kernels.EgnnTable for the first graph layer when first_layer_table selects it and the layer's shape allows it, else
+        None.  The grid problem's per-node projections are mdx_egnn_node_inputs' second output for one node per class at
+        sigma[0]: the arithmetic of the batch's own first_proj."""
+        from ... import kernels
+        mode = self.first_layer_table
+        if mode not in ("auto", "on", "off"):
+            raise ValueError(f"first_layer_table should be auto, on or off. Got {mode}")
+        if mode == "off" or (mode == "auto" and not self.sigma_uniform_hint):
+            return None
+        layer = self.egnn.graph_layers[0]
+        if not layer.table_applies(layer._edge_chain_pack(), h, z):
+            return None
+        n_classes = self.num_atom_types + 1
+        n_even = kernels.egnn_table_points(z.shape[1])
+        if mode == "auto" and n_classes ** 2 * (2 * n_even - 1) * 8 > edges.shape[0]:
+            return None
+        classes, _, _ = kernels.egnn_table_grid(n_classes, n_even, z.shape[1], z.device)
+        G = classes.shape[0]
+        grid_x = self.__dict__.get("_table_grid_x")
+        if grid_x is None or grid_x.shape[1] != G or grid_x.device != z.device:
+            grid_x = self._table_grid_x = torch.zeros(1, G, 3, dtype=torch.float32, device=z.device)
+        sigma = sigma.to(device=z.device, dtype=torch.float32).reshape(-1).contiguous()
+        emb = self.egnn.embedding_in
+        _, _, grid_proj = kernels.egnn_node_inputs(grid_x, k_vectors.contiguous(), sigma, classes.reshape(1, G),
+                                                   emb.weight.detach().contiguous(), emb.bias.detach().contiguous(), second=second)
+        return kernels.EgnnTable(grid_proj=grid_proj, sigma=sigma, atom_types=atom_types.reshape(-1).long().contiguous(),
+                                 n_classes=n_classes, n_even=n_even)
 
     def _make_egnn(self, hp):
         return EGNN(
@@ -310,17 +347,19 @@ class EGNNScoreNetwork(ScoreNetwork):
                                            comp.A.reshape(bsz, n).long().contiguous(), emb.weight.detach().contiguous(),
                                            emb.bias.detach().contiguous(), second=second)
             z, h, first_proj = res if second is not None else (res[0], res[1], None)
+            table = self._first_layer_table(edges, z, h, sigma_in, comp.A, k_vectors, second) if second is not None else None
             head = self.egnn.node_classification_layer
             if head.out_features <= 8 and head.in_features % 4 == 0 and comp.L.dtype == torch.float32:
                 # classification layer (MASK logit at -inf), scores and the zero lattice output: one launch
-                out = self.egnn(h=h, edges=edges, x=z, degree=degree, embedded=True, first_proj=first_proj, classify=False)
+                out = self.egnn(h=h, edges=edges, x=z, degree=degree, embedded=True, first_proj=first_proj, classify=False,
+                                first_table=table)
                 scores, logits, zeros = kernels.egnn_outputs(
                     z, out.X.contiguous(), k_vectors.contiguous(), out.A.contiguous(), head.weight.detach().contiguous(),
                     head.bias.detach().contiguous(), self.num_atom_types, comp.L.numel())
                 logits = logits.reshape(bsz, n, -1)
                 logits._mdx_mask_imposed = True
                 return AXL(A=logits, X=scores.reshape(bsz, n, d), L=zeros.reshape(comp.L.shape))
-            out = self.egnn(h=h, edges=edges, x=z, degree=degree, embedded=True, first_proj=first_proj)
+            out = self.egnn(h=h, edges=edges, x=z, degree=degree, embedded=True, first_proj=first_proj, first_table=table)
             scores = kernels.egnn_scores(z, out.X.contiguous(), k_vectors.contiguous())
             return AXL(A=out.A.reshape(bsz, n, -1), X=scores.reshape(bsz, n, d), L=torch.zeros_like(comp.L))
 

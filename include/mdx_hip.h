@@ -42,6 +42,9 @@ extern "C" {
 #define MDX_STATUS_MASK_AT_LAST_STEP 2u  /* generators/langevin_generator.py:616-620 assert */
 #define MDX_STATUS_EGNN_F16_RANGE 4u     /* mdx_egnn_edge_chain, split-f16 mode: an activation left the f16 range     */
 #define MDX_STATUS_GRAPH_CAPACITY 8u     /* mdx_radius_graph_fill_capped: more edges than the caller's capacity      */
+#define MDX_STATUS_EGNN_TABLE 16u        /* mdx_egnn_table_check / _gather: the first layer's distance table does not
+                                            stand in for the per-edge chain (interpolation error, sigma not uniform,
+                                            a distance or class outside the table) -- recompute on the per-edge chain */
 
 #define MDX_MAX_CLASSES 8      /* C supported by the fused atom-type kernels */
 #define MDX_PREDICTOR 0
@@ -496,6 +499,30 @@ MDX_API int mdx_egnn_node_gather(const float* pieces, int64_t n_edges, const int
                                  int64_t n_nodes, int H, int mean_messages, const float* left, float* out,
                                  const float* edge_scalar, const float* coord, int coord_dimension, const int64_t* edges,
                                  int mean_coords, int coord_flags, float* coord_out, mdx_stream_t stream);
+
+/* The first graph layer of a sampler forward on a distance grid (csrc/mdx_egnn_table.hip).  With one
+ * sigma per batch the layer's per-edge output (messages [H] and the coordinate head's raw scalar) is a function F_ab(rho) of the
+ * class pair (a, b) -- atom type, MASK = n_classes - 1 -- and of rho = sqrt(|c_i - c_j|^2).  `table` [n_classes^2 K, H] and
+ * `table_scalar` [n_classes^2 K] are mdx_egnn_edge_chain's MDX_EGNN_MESSAGES_ROWS outputs on the grid problem: class pair
+ * p = a n_classes + b owns rows [p K, p K + K), K = 2 n_even - 1; row p K + m is rho = m h (m < n_even), row p K + n_even + j the
+ * cell midpoint rho = (j + 1/2) h (j < n_even - 1), h = 1 / inv_spacing.
+ * mdx_egnn_table_check: the 4-point Lagrange interpolation of the even points at the midpoints j <= n_even - 3 against the
+ *   chain's values there, per class pair and column (the scalar is column H), relative to the class pair's largest |value| over
+ *   all its columns; ORs MDX_STATUS_EGNN_TABLE into status when an error exceeds `tolerance` or sigma[0 .. n_sigma) is not
+ *   uniform.  workspace: device, uint32 [n_classes^2 (H + 2)], zero-filled once by the caller (the call leaves it zeroed);
+ *   worst_out (nullable): device float [1], the largest relative error.  Two launches, no host synchronisation.
+ * mdx_egnn_table_gather: the output contract of mdx_egnn_node_gather with the messages and scalars interpolated per edge from
+ *   the table (even symmetry at rho = 0): out = [left | message sums] (or the sums), coord_out; atom_types [n_nodes] in
+ *   [0, n_classes).  A distance beyond the grid or a class outside it ORs MDX_STATUS_EGNN_TABLE into status (nullable).
+ *   H % 4 == 0, H <= 256, coord_dimension <= 8. */
+MDX_API int mdx_egnn_table_check(const float* table, const float* table_scalar, int H, int n_classes, int n_even,
+                                 const float* sigma, int64_t n_sigma, float tolerance, uint32_t* workspace, float* worst_out,
+                                 uint32_t* status, mdx_stream_t stream);
+MDX_API int mdx_egnn_table_gather(const float* table, const float* table_scalar, int H, int n_classes, int n_even,
+                                  float inv_spacing, const int64_t* atom_types, const int64_t* offsets, const int64_t* degree,
+                                  int64_t n_nodes, int mean_messages, const float* left, float* out, const float* coord,
+                                  int coord_dimension, const int64_t* edges, int mean_coords, int coord_flags, float* coord_out,
+                                  uint32_t* status, mdx_stream_t stream);
 
 /* EGNNScoreNetwork's per-node inputs and outputs around the EGNN (models/score_networks/egnn_score_network.py:253-290), one
  * launch each instead of a dozen elementwise passes (spatial dimension 3):
