@@ -10,6 +10,8 @@
 //   repaint_rows_kernel    R1  forward-noise + scatter of the constrained rows (F1 + F2 fused)
 //   radius_graph_kernel    N1  27-image radius graph, structure tile staged in LDS, one wavefront per source
 //                              row, ballot/scan ranked writes => edges come out sorted, no atomics
+//   force_field_kernel         the force-field wrapper's pseudo-force on N1's tile and pair test, no edge list:
+//                              per-lane sums + a fixed cross-lane reduction, optional fused add to the score
 //   rng_fill_kernel            Philox draws as arrays
 // 64-wide wavefronts are assumed throughout (gfx950).
 #include <hip/hip_runtime.h>
@@ -2060,6 +2062,92 @@ __global__ __launch_bounds__(kBlock) void radius_graph_kernel(const float* __res
     }
 }
 
+// The force-field wrapper's pseudo-force (force_field_augmented_score_network.py:86-236) straight from the coordinates: the
+// staging, the image set and the hit predicate of radius_graph_kernel in its lattice mode (so the edges are the ones the full
+// radius graph lists), and the reference's arithmetic per hit (i, j, image l):
+//   disp = (p_j - p_i) + shift_l,  r = |disp|,  c = two_s (r - rc) / (r + 1e-8) disp
+// Each lane sums its own hits; a fixed xor-butterfly over the 64 lanes then gives the row's sum, so a row depends on nothing but
+// its structure.  F_rel = F_cart x (1 / L) (the reference's matmul with inverse(diag(L)): its off-diagonal terms are exact zeros)
+// is rounded before the optional add of score_in -- the bits of raw.X + forces.  No edge list, no atomics, no workspace.
+__global__ __launch_bounds__(kBlock) void force_field_kernel(const float* __restrict__ relative, const float* __restrict__ lattice,
+                                                             int lattice_stride, float clip_min, float rc, float two_s, int N,
+                                                             int chunks, const float* __restrict__ score_in,
+                                                             float* __restrict__ out, uint32_t* status)
+{
+    extern __shared__ float lds[];
+    float* pos = lds;            // [N][3]
+    float* lv = lds + 3 * N;     // [27][3]
+    const int64_t b = blockIdx.x / chunks;
+    const int chunk = blockIdx.x % chunks;
+    const float* P = relative + b * N * 3;
+    float cl[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) cl[k] = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float v = lattice[b * lattice_stride + k];
+        cl[4 * k] = v < clip_min ? clip_min : v;              // torch.clip(min=): a NaN stays a NaN
+    }
+    for (int i = threadIdx.x; i < 3 * N; i += blockDim.x) {
+        const int c = i % 3;
+        pos[i] = P[i] * (c == 0 ? cl[0] : c == 1 ? cl[4] : cl[8]);
+    }
+    if (threadIdx.x < 81) {
+        const int l = threadIdx.x / 3, c = threadIdx.x % 3;
+        const float rel[3] = {(float)(l / 9 - 1), (float)((l / 3) % 3 - 1), (float)(l % 3 - 1)};
+        float acc = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) acc = __builtin_fmaf(rel[k], c == 0 ? cl[k * 3] : c == 1 ? cl[k * 3 + 1] : cl[k * 3 + 2], acc);
+        lv[threadIdx.x] = acc;
+    }
+    if (chunk == 0 && threadIdx.x == 96 && status) {
+        if (!(crossing_distance(cl) > rc)) atomicOr(status, MDX_STATUS_CUTOFF_TOO_LARGE);
+    }
+    const bool ortho = cl[0] > 0.0f && cl[4] > 0.0f && cl[8] > 0.0f && rc * 2.2f <= fminf(cl[0], fminf(cl[4], cl[8]));
+    const float inv_lx = ortho ? 1.0f / cl[0] : 0.0f, inv_ly = ortho ? 1.0f / cl[4] : 0.0f,
+                inv_lz = ortho ? 1.0f / cl[8] : 0.0f;
+    // relative = cartesian x inverse(diag(L)): the reciprocal of the clipped length, then one product per component
+    const float rx = 1.0f / cl[0], ry = 1.0f / cl[4], rz = 1.0f / cl[8];
+    __syncthreads();
+    const float rc2 = rc * rc;
+    const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+    const int row_end = min(N, (chunk + 1) * kRowsPerBlock);
+    for (int i = chunk * kRowsPerBlock + wave; i < row_end; i += kBlock / kWave) {
+        const float pix = pos[3 * i], piy = pos[3 * i + 1], piz = pos[3 * i + 2];
+        float fx = 0.0f, fy = 0.0f, fz = 0.0f;
+        for (int j0 = 0; j0 < N; j0 += kWave) {
+            const int j = j0 + lane;
+            if (j >= N) continue;
+            const float pjx = pos[3 * j], pjy = pos[3 * j + 1], pjz = pos[3 * j + 2];
+            uint32_t m = images_within_cutoff(ortho, pix, piy, piz, pjx, pjy, pjz, inv_lx, inv_ly, inv_lz, cl[0], cl[4], cl[8],
+                                              lv, rc2);
+            while (m) {
+                const int l = __ffs(m) - 1;
+                m &= m - 1;
+                const float dx = (pjx - pix) + lv[3 * l], dy = (pjy - piy) + lv[3 * l + 1], dz = (pjz - piz) + lv[3 * l + 2];
+                const float r = __builtin_sqrtf((dx * dx + dy * dy) + dz * dz);
+                const float c = two_s * (r - rc) / (r + 1.0e-8f);
+                fx += c * dx;
+                fy += c * dy;
+                fz += c * dz;
+            }
+        }
+#pragma unroll
+        for (int o = kWave / 2; o > 0; o >>= 1) {
+            fx += __shfl_xor(fx, o, kWave);
+            fy += __shfl_xor(fy, o, kWave);
+            fz += __shfl_xor(fz, o, kWave);
+        }
+        if (lane == 0) {
+            const int64_t row = (b * N + i) * 3;
+            const float gx = fx * rx, gy = fy * ry, gz = fz * rz;
+            out[row] = score_in ? score_in[row] + gx : gx;
+            out[row + 1] = score_in ? score_in[row + 1] + gy : gy;
+            out[row + 2] = score_in ? score_in[row + 2] + gz : gz;
+        }
+    }
+}
+
 // offsets[i] = counts[0] + ... + counts[i-1], *total = the sum: ONE workgroup walks the list in tiles of 16 384 entries (the list is
 // the per-atom edge count of a batch -- 32 768 entries, two tiles, at C3; a launch of its own between the two radius-graph passes
 // costs less than the three library launches of cumsum + subtraction it replaces).  A tile is kScanRows rows of 2 x kScanBlock
@@ -2772,6 +2860,22 @@ int mdx_egnn_radius_graph(const float* relative_coordinates, const float* lattic
     hipLaunchKernelGGL(radius_graph_kernel<true>, grid, dim3(kBlock), lds, as_stream(stream), relative_coordinates,
                        (const float*)nullptr, rc, batch, N, 1, chunks, (int64_t*)nullptr, (const int64_t*)offsets, edges_out,
                        (int32_t*)nullptr, (float*)nullptr, status, capacity, lattice_parameters, lattice_stride, clip_min);
+    return launch_status();
+}
+
+int mdx_force_field_pseudo_force(const float* relative_coordinates, const float* lattice_parameters, int lattice_stride,
+                                 float clip_min, float rc, float two_strength, int64_t batch, int N, const float* score_in,
+                                 float* out, uint32_t* status, mdx_stream_t stream)
+{
+    if (batch < 0 || N < 1 || !(rc > 0.0f) || lattice_stride < 3 || !(clip_min >= 0.0f)) return MDX_ERR_INVALID_ARG;
+    if (N > 5000) return MDX_ERR_UNSUPPORTED;    // the structure tile in LDS, as the radius graph's
+    if (batch == 0) return MDX_OK;
+    if (!relative_coordinates || !lattice_parameters || !out) return MDX_ERR_INVALID_ARG;
+    const int chunks = (int)cdiv(N, kRowsPerBlock);
+    const size_t lds = sizeof(float) * (3 * (size_t)N + 81);
+    hipLaunchKernelGGL(force_field_kernel, dim3((unsigned)(batch * chunks)), dim3(kBlock), lds, as_stream(stream),
+                       relative_coordinates, lattice_parameters, lattice_stride, clip_min, rc, two_strength, N, chunks, score_in,
+                       out, status);
     return launch_status();
 }
 

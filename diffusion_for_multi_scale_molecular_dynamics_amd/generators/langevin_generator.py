@@ -670,8 +670,11 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
                     self.one_atom_type_transition_per_step, self.atom_type_transition_in_corrector,
                     self.use_fixed_lattice_parameters, self.small_epsilon, self.num_classes)     # kernel arguments of the capture
         words = tuple(None if w is None else w.data_ptr() for w in (self._call_word, self._status))   # read by the captured kernels
+        # the force-field wrapper's cutoff and strength are kernel arguments too: their values, not the (mutable) object
+        force_field = getattr(net, "force_field_parameters", None)
         return (tuple(start.X.shape), tuple(start.L.shape), str(start.X.device), getattr(net, "edge_chain_precision", None),
                 getattr(net, "first_layer_table", None), settings, words,
+                None if force_field is None else dataclasses.astuple(force_field),
                 tuple((p.data_ptr(), p._version) for p in net.parameters()))
 
     def _sample_with_graph(self, start: AXL, starting_step_index: int, ending_step_index: int) -> AXL:

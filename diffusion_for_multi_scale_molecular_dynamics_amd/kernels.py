@@ -314,6 +314,27 @@ def egnn_radius_graph(relative_coordinates, lattice_parameters, clip_min: float,
     return dict(counts=counts, offsets=offsets, edges=edges, n_edges=n_edges)
 
 
+def force_field_pseudo_force(relative_coordinates, lattice_parameters, clip_min: float, radial_cutoff: float, strength: float,
+                             score_in: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The force-field wrapper's repulsive pseudo-force in relative coordinates [B,N,3] (mdx_force_field_pseudo_force): every
+    (i, j, image) pair of the full radius graph of relative coordinates [B,N,3] in the cell diag(max(lattice_parameters[:, :3],
+    clip_min)), tested in place -- one launch, no edge list, no host read.  With `score_in` [B,N,3] the result is score_in + the
+    pseudo-force.  MDX_STATUS_CUTOFF_TOO_LARGE is OR-ed into `status` where the cutoff reaches the cell's crossing distance."""
+    B, N, d = relative_coordinates.shape
+    if d != 3:
+        raise _hip.MdxError(f"force-field pseudo-force: spatial dimension 3 only (the reference's), got {d}")
+    assert lattice_parameters.dim() == 2 and lattice_parameters.shape[0] == B and lattice_parameters.shape[1] >= 3
+    if score_in is not None and score_in.shape != relative_coordinates.shape:
+        raise ValueError(f"score_in has shape {tuple(score_in.shape)}, expected {tuple(relative_coordinates.shape)}")
+    out = torch.empty(B, N, 3, dtype=F32, device=relative_coordinates.device)
+    check(lib().mdx_force_field_pseudo_force(ptr(relative_coordinates, F32, "relative_coordinates"),
+                                             ptr(lattice_parameters, F32, "lattice_parameters"), lattice_parameters.shape[1],
+                                             float(clip_min), float(radial_cutoff), float(2.0 * strength), B, N,
+                                             ptr(score_in, F32, "score_in"), ptr(out, F32, "out"), ptr(status, I32, "status"),
+                                             stream_handle()), "mdx_force_field_pseudo_force")
+    return out
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # fused MLP score network
 # ----------------------------------------------------------------------------------------------------------------

@@ -267,6 +267,23 @@ MDX_API int mdx_egnn_radius_graph(const float* relative_coordinates, const float
                                   int64_t* counts, int64_t* offsets, int64_t* n_edges, int64_t* edges_out, uint32_t* status,
                                   uint64_t* workspace, int64_t workspace_words, mdx_stream_t stream);
 
+/* The pseudo-force of ForceFieldAugmentedScoreNetwork (models/score_networks/force_field_augmented_score_network.py:86-236,
+ * with utils/neighbors.py:36-224 and utils/basis_transformations.py:230-256): phi(r) = s (r - rc)^2 over every (i, j, image)
+ * pair of the full radius graph of RELATIVE coordinates [batch, N, 3] in the cell diag(max(lattice_parameters[b, 0..2],
+ * clip_min)) (the reference's min_box_size; lattice_stride as mdx_egnn_radius_graph), returned in relative coordinates:
+ *   out[b, i] = (sum_{j, l} two_strength (r - rc) / (r + 1e-8) disp) x (1 / L),  disp = (p_j - p_i) + shift_l,  r = |disp|
+ * two_strength = (float)(2.0 * strength), formed in double as the reference's Python does.  The pairs are the ones
+ * mdx_radius_graph_count / _fill list (0 < d^2 <= rc^2, 27 images), tested in place: no edge list, no atomics, no workspace,
+ * no host read.  A row's sum is a fixed-order reduction: it does not depend on the rest of the batch or on the run.
+ * score_in (nullable, [batch, N, 3]): out = score_in + pseudo-force (the reference's raw.X + forces, same bits).
+ * status (nullable): MDX_STATUS_CUTOFF_TOO_LARGE is OR-ed in where rc reaches the cell's crossing distance (the reference's
+ * assert, neighbors.py:107-113).  Spatial dimension 3 only (the reference's :131-135); N <= 5000 (LDS), else
+ * MDX_ERR_UNSUPPORTED. */
+MDX_API int mdx_force_field_pseudo_force(const float* relative_coordinates, const float* lattice_parameters, int lattice_stride,
+                                         float clip_min, float radial_cutoff, float two_strength, int64_t batch,
+                                         int number_of_atoms, const float* score_in, float* out, uint32_t* status,
+                                         mdx_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Fused score network: the reference's MLPScoreNetwork (models/score_networks/mlp_score_network.py:54-370,
  * unconditional forward, no permutation symmetrisation, no time prefactor) evaluated inside the kernels.
