@@ -12,7 +12,7 @@ from typing import Optional
 import torch
 
 from .. import kernels
-from .._hip import MDX_CORRECTOR, MDX_PREDICTOR, TAG_COORD, TAG_LATTICE, MdxError
+from .._hip import MDX_CORRECTOR, MDX_PREDICTOR, STATUS_MASK_AT_LAST_STEP, TAG_COORD, TAG_LATTICE, MdxError
 from ..models.score_networks.score_network import ScoreNetwork
 from ..namespace import AXL
 from ..noise_schedulers.noise_parameters import NoiseParameters
@@ -49,7 +49,7 @@ class AdaptiveCorrectorGenerator(LangevinGenerator):
         kernels.fill_time_sigma(sched, MDX_PREDICTOR, index_i, None, time_t, sigma_t)
         predictions = self._get_model_predictions(composition_i, time_t, sigma_t, cartesian_forces)
         idx = index_i - 1
-        device_rng = getattr(self.noise_source, "device_rng", False)
+        device_rng = self._device_rng
         if device_rng:
             draw = index_i * (self.number_of_corrector_steps + 1)
             src = self.noise_source
@@ -69,7 +69,7 @@ class AdaptiveCorrectorGenerator(LangevinGenerator):
                                           sched.q_bar_matrix[idx], sched.q_bar_tm1_matrix[idx], gumbel, u,
                                           self.small_epsilon, self.atom_type_greedy_sampling, one)
         if idx == 0:
-            self._status |= ((a_im1 == self.masked_atom_type_index).any().to(torch.int32) * 2)
+            self._status |= (a_im1 == self.masked_atom_type_index).any().to(torch.int32) * STATUS_MASK_AT_LAST_STEP
         out = AXL(A=a_im1, X=composition_i.X, L=composition_i.L)
         if self.record:
             self._record_step("predictor_step", ["composition_i", "composition_im1", "model_predictions_i"],
@@ -95,7 +95,7 @@ class AdaptiveCorrectorGenerator(LangevinGenerator):
         kernels.fill_time_sigma(sched, MDX_CORRECTOR, index_i, None, time_t, sigma_t)
         predictions = self._get_model_predictions(composition_i, time_t, sigma_t, cartesian_forces)
         sigma = sigma_t[0, 0]
-        device_rng = getattr(self.noise_source, "device_rng", False)
+        device_rng = self._device_rng
         if device_rng:
             z = self._normal(batch, index_i, 1 + corrector_number, TAG_COORD, batch * n, d, device).view(batch, n, d)
         else:

@@ -58,7 +58,7 @@ class ConstrainedLangevinGenerator(LangevinGenerator):
         sched = self._prepare(device)
         cx, ca, cidx = self._constraint_on(device)
         z = u = None
-        if not getattr(self.noise_source, "device_rng", False):
+        if not self._device_rng:
             self.initialize(batch, device)                     # composition_0_known: drawn, only constrained rows kept
             if d_index is None and index_i > 0:                # noising_transform.py:154,179
                 z = upload(self.noise_source.randn(x.shape), device)
@@ -77,7 +77,7 @@ class ConstrainedLangevinGenerator(LangevinGenerator):
         x, a = composition.X, composition.A
         device = x.device
         z = u = None
-        if not getattr(self.noise_source, "device_rng", False):
+        if not self._device_rng:
             z = upload(self.noise_source.randn(x.shape), device)
             u = upload(self.noise_source.rand(x.shape[0], self.number_of_atoms, self.num_classes), device)
         kernels.forward_diffusion_step(self._prepare(device), index_i, d_index, z, u, self._rng(0), x, a)

@@ -12,14 +12,17 @@ Same class name, constructor, step methods and behaviour as the reference's Lang
     watched per ITERATION: in the device-resident loop through asynchronous copies to page-locked memory read two
     iterations behind the queue, so the device never waits for the host -- IterationLoop._advance_watched; in the eager
     loop -- reference-order RNG, recording runs, callers without a hipGraph -- by ONE blocking 4-byte read per iteration
-    (_take_range_report): that loop already uploads the iteration's draws from the host, it is the parity path, not the
-    fast one);
+    (_guarded_iteration): that loop already uploads the iteration's draws from the host, it is the parity path, not the
+    fast one.  Both hand a report to LangevinGenerator._recover; what a sampler may ask of a network is network_hooks.py);
   * rng_mode="device" removes the per-step CPU draws + PCIe uploads, and use_hip_graph=True replays one captured
     predictor+correctors iteration T times with the step index living on the device.
 
 There is no CPU fallback: calling this generator with device="cpu" raises.
 """
 import dataclasses
+import gc
+import warnings
+import weakref
 from typing import Optional
 
 import torch
@@ -32,6 +35,7 @@ from ..namespace import AXL, CARTESIAN_FORCES, NOISE, NOISY_AXL_COMPOSITION, TIM
 from ..noise_schedulers.noise_parameters import NoiseParameters
 from ..noise_schedulers.noise_scheduler import NoiseScheduler
 from ..utils.sample_trajectory import PinnedStaging, SampleTrajectory
+from . import network_hooks as hooks
 from .noise_sources import DevicePhiloxNoise, RecordingNoise, ReferenceOrderNoise, one_host_thread, upload
 from .predictor_corrector_axl_generator import PredictorCorrectorAXLGenerator, PredictorCorrectorSamplingParameters
 from .trajectory_initializer import TrajectoryInitializer
@@ -79,11 +83,12 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
         self._call_counter = 0
         self.noise_source = ReferenceOrderNoise() if rng_mode == "reference" else None
         # ITERATIONS recomputed with the exact-f32 MFMA kernels because the split-f16 ones met a value beyond the f16 range
-        # (_guarded_iteration, IterationLoop._advance_watched); logged by sample_diffusion, printed by bench.py
+        # (_recover); logged by sample_diffusion, printed by bench.py
         self.f16_range_fallbacks = 0
         self.table_fallbacks = 0         # MDX_STATUS_EGNN_TABLE reports (the network's first layer left the distance table)
         self.resampling_steps = 0     # set by ConstrainedLangevinGenerator (repaint_resampling_steps)
         self._visit = 0               # which of the 1 + resampling_steps passes through the current time index
+        self._warned_not_capturable = False
 
         self._scheduler = None       # device tables, built on first use for the sampling device
         self._status = None
@@ -99,6 +104,12 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
     # ---------------------------------------------------------------------------------------------------------
     # device state
     # ---------------------------------------------------------------------------------------------------------
+    @property
+    def _device_rng(self) -> bool:
+        """Does the noise source draw inside the kernels (DevicePhiloxNoise)?  A caller's own source without the attribute
+        draws on the host."""
+        return getattr(self.noise_source, "device_rng", False)
+
     @staticmethod
     def _device(device) -> torch.device:
         """`cuda` -> `cuda:<current>`: torch.device("cuda") != torch.device("cuda:0"), and everything this generator keeps per
@@ -143,8 +154,8 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
         _begin_call) as well as by value: a launch captured into a hipGraph reads the word, so the same graph serves every
         later sample() call of that shape."""
         src = self.noise_source
-        seed, call = (src.seed, src.call) if getattr(src, "device_rng", False) else (0, 0)
-        word = self._call_word.data_ptr() if getattr(src, "device_rng", False) and self._call_word is not None else None
+        seed, call = (src.seed, src.call) if self._device_rng else (0, 0)
+        word = self._call_word.data_ptr() if self._device_rng and self._call_word is not None else None
         return Rng(seed, call, self._draw_stride(),
                    self._visit * (self.number_of_corrector_steps + 1) + draw_offset, 0, word)
 
@@ -300,15 +311,8 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
         if not isinstance(sigma_noise, torch.Tensor) or sigma_noise.dim() == 0:
             sigma_noise = torch.full((composition.X.shape[0], 1), float(sigma_noise), dtype=torch.float32, device=composition.X.device)
         batch = {NOISY_AXL_COMPOSITION: composition, TIME: time, NOISE: sigma_noise, CARTESIAN_FORCES: cartesian_forces}
-        net = self.axl_network
-        if not hasattr(net, "sigma_uniform_hint"):
-            return net(batch, conditional=False)
-        # (the loop fills one sigma for the whole batch: the network may run its first graph layer on a distance grid)
-        net.sigma_uniform_hint = True
-        try:
-            return net(batch, conditional=False)
-        finally:
-            net.sigma_uniform_hint = False
+        with hooks.uniform_sigma(self.axl_network):        # (the loop fills one sigma for the whole batch)
+            return self.axl_network(batch, conditional=False)
 
     # ---------------------------------------------------------------------------------------------------------
     # one step = network forward + ONE fused update kernel
@@ -325,7 +329,7 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
 
         update_types = mode == MDX_PREDICTOR or self.atom_type_transition_in_corrector
         z = gumbel = u = z_lattice = None
-        if not getattr(self.noise_source, "device_rng", False):
+        if not self._device_rng:
             if mode == MDX_PREDICTOR:                                  # langevin_generator.py:280,416,623,633
                 gumbel = self._draw_gumbel_sample(batch)
                 if self.atom_type_greedy_sampling:
@@ -447,80 +451,28 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
         return out
 
     # ---------------------------------------------------------------------------------------------------------
-    # the f16 range of the score network's split-f16 MFMA kernels, handled per ITERATION
+    # the score network's reports (its f16 range, its first-layer table), handled per ITERATION
     # ---------------------------------------------------------------------------------------------------------
-    SPLIT_F16_MODES = ("f16x3", "f16x3_32x32")
-
-    REPORTS = STATUS_EGNN_F16_RANGE | STATUS_EGNN_TABLE
-
-    def _range_guarded(self) -> bool:
-        """Does the score network run split-f16 kernels that can report a value beyond the f16 range, or a first-layer
-        distance table that can report MDX_STATUS_EGNN_TABLE?"""
-        net = self.axl_network
-        return getattr(net, "edge_chain_precision", None) in self.SPLIT_F16_MODES or \
-            getattr(net, "first_layer_table", "off") != "off"
-
-    def _take_range_report(self) -> int:
-        """Read the network's status word (a host synchronisation) and clear its f16-range and table bits: the ones of those
-        that were set (other bits stay for check_status())."""
-        status = getattr(self.axl_network, "graph_status", None)
-        if status is None:
-            return 0
-        word = int(status.item()) & self.REPORTS
-        if word:
-            status.bitwise_and_(~self.REPORTS)
-        return word
-
-    def _count_table_fallback(self, index_i: int):
-        """MDX_STATUS_EGNN_TABLE: the network's first layer goes back to the per-edge chain for the rest of the process."""
-        import warnings
-        self.table_fallbacks += 1
-        self.axl_network.first_layer_table = "off"
-        warnings.warn(f"EGNN first layer: the distance table failed its check at time index {index_i}; this iteration is "
-                      "recomputed on the per-edge chain, and the network's first_layer_table is now 'off'")
-
-    def _recompute(self, report: int, run):
-        """run() with what a report asks for: the exact-f32 kernels for this call (f16 range), the per-edge first layer from
-        now on (table)."""
-        net = self.axl_network
+    def _recover(self, report: int, index_i: int, run):
+        """run() again after the score network's `report` (network_hooks.REPORTS) on the iteration at time index `index_i`, whose
+        effects the caller has dropped; counted and warned about.  An f16-range report: under the exact-f32 kernels, for this
+        run only.  A table report: on the per-edge first layer, from now on."""
+        # what the dropped attempt raised in the generator's own word goes with it (non-finite logits at time index 0 leave
+        # MASKs behind: MDX_STATUS_MASK_AT_LAST_STEP, the one bit this word holds) -- run() raises it again if it is real
+        self._status.zero_()
+        if report & STATUS_EGNN_F16_RANGE:
+            self.f16_range_fallbacks += 1
+            warnings.warn(f"EGNN edge chain: a value beyond the f16 range at time index {index_i}; this iteration is recomputed "
+                          "with edge_chain_precision='f32' on the same draws (the network's setting is restored afterwards)")
+        if report & STATUS_EGNN_TABLE:
+            self.table_fallbacks += 1
+            hooks.table_off(self.axl_network)
+            warnings.warn(f"EGNN first layer: the distance table failed its check at time index {index_i}; this iteration is "
+                          "recomputed on the per-edge chain, and the network's first_layer_table is now 'off'")
         if not report & STATUS_EGNN_F16_RANGE:
             return run()
-        precision = net.edge_chain_precision
-        self._begin_f16_fallback()
-        net.edge_chain_precision = "f32"
-        try:
+        with hooks.exact_f32(self.axl_network):
             return run()
-        finally:
-            net.edge_chain_precision = precision
-            self._adapt_f16_range()
-
-    def _adapt_f16_range(self):
-        """After the exact-f32 pass: the network derives per-layer activation exponents for its split-f16 kernels from the
-        maxima that pass has collected (EGNNScoreNetwork.adapt_f16_range), so a layer that runs hot does not send every
-        following iteration through the f32 kernels."""
-        adapt = getattr(self.axl_network, "adapt_f16_range", None)
-        if adapt is not None:
-            adapt()
-
-    def _begin_f16_fallback(self):
-        """Before the exact-f32 pass of a fallback: the network forgets the activation maxima earlier f32 launches left (plain
-        f32 use, other inputs), so the exponents adapt() derives afterwards describe THIS iteration."""
-        begin = getattr(self.axl_network, "begin_f16_range_fallback", None)
-        if begin is not None:
-            begin()
-
-    def _clear_stale_range_report(self):
-        """A range bit left in the network's word by something that was not an iteration of this loop (the warm-up iterations
-        before a capture, a caller stepping by hand) must not be read as the first iteration's report."""
-        status = getattr(self.axl_network, "graph_status", None)
-        if status is not None and self._range_guarded():
-            status.bitwise_and_(~self.REPORTS)
-
-    def _count_fallback(self, index_i: int):
-        import warnings
-        self.f16_range_fallbacks += 1
-        warnings.warn(f"EGNN edge chain: a value beyond the f16 range at time index {index_i}; this iteration is recomputed with "
-                      "edge_chain_precision='f32' on the same draws (the network's setting is restored afterwards)")
 
     def _iteration(self, composition: AXL, i: int, forces: torch.Tensor) -> AXL:
         """Time index i + 1 -> i: predictor, M correctors, and the resampling passes of the repaint generator."""
@@ -535,37 +487,30 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
         return composition
 
     def _guarded_iteration(self, composition: AXL, i: int, forces: torch.Tensor) -> AXL:
-        """_iteration(); if the score network's split-f16 kernels report a value beyond the f16 range, THAT iteration -- and
-        nothing else -- is recomputed from the same composition with the exact-f32 kernels on the same draws: the network's
-        precision is put back afterwards, what the discarded attempt recorded is dropped, the event is counted in
-        `f16_range_fallbacks` and warned about.  Device RNG: a draw is a function of (seed, call, index).  Reference-order RNG:
-        the iteration's draws are kept while it runs and handed out again (one iteration's worth, not the trajectory's)."""
-        if not self._range_guarded():
+        """_iteration(); if the score network reports on it (network_hooks.REPORTS), THAT iteration -- and nothing else -- is run
+        again by _recover from the same composition on the same draws, and what the discarded attempt recorded is dropped.
+        Device RNG: a draw is a function of (seed, call, index).  Reference-order RNG: the iteration's draws are kept while it
+        runs and handed out again (one iteration's worth, not the trajectory's)."""
+        if not hooks.reports_watched(self.axl_network):
             return self._iteration(composition, i, forces)
-        net, source = self.axl_network, self.noise_source
-        keeps = not getattr(source, "device_rng", False)
+        source, keeps = self.noise_source, not self._device_rng
         if keeps:
             self.noise_source = RecordingNoise(source)
             self._share_noise_source()
         marks = self._recorder_marks() if self.record else None
-        try:
-            out = self._iteration(composition, i, forces)
-            report = self._take_range_report()
-            if not report:
-                return out
-            if report & STATUS_EGNN_F16_RANGE:
-                self._count_fallback(i)
-            if report & STATUS_EGNN_TABLE:
-                self._count_table_fallback(i)
+
+        def again():
             if marks is not None:
                 self._recorder_truncate(marks)
             if keeps:
                 self.noise_source = self.noise_source.replay()
                 self._share_noise_source()
-            # what the dropped attempt raised in the generator's own word goes with it (non-finite logits at time index 0 leave
-            # MASKs behind: MDX_STATUS_MASK_AT_LAST_STEP) -- the exact-f32 pass raises it again if it is real
-            self._status.bitwise_and_(~STATUS_MASK_AT_LAST_STEP)
-            return self._recompute(report, lambda: self._iteration(composition, i, forces))
+            return self._iteration(composition, i, forces)
+
+        try:
+            out = self._iteration(composition, i, forces)
+            report = hooks.take_reports(self.axl_network)
+            return self._recover(report, i, again) if report else out
         finally:
             if keeps:
                 self.noise_source = source
@@ -588,27 +533,20 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
     def _run_loop(self, starting_noisy_composition: AXL, starting_step_index: int, ending_step_index: int) -> AXL:
         if self.fused_score_network:
             return self._sample_fused(starting_noisy_composition, starting_step_index, ending_step_index)
-        if self.use_hip_graph and getattr(self.noise_source, "device_rng", False) and not self.record and \
-                self._network_is_capture_safe(starting_noisy_composition):
+        if self.use_hip_graph and self._device_rng and not self.record and self._capture_safe(starting_noisy_composition):
             return self._sample_with_graph(starting_noisy_composition, starting_step_index, ending_step_index)
         composition = starting_noisy_composition
         forces = torch.zeros_like(composition.X)
-        self._clear_stale_range_report()
+        hooks.clear_reports(self.axl_network)
         for i in range(starting_step_index - 1, max(ending_step_index, 0) - 1, -1):
             composition = self._guarded_iteration(composition, i, forces)
         return composition
 
-    def _network_is_capture_safe(self, composition: AXL) -> bool:
-        """A score network may say that its forward on this batch shape needs a host synchronisation (`capture_safe(batch,
-        atoms, device)`: EGNNScoreNetwork with a radius graph whose layers do not all run the fused edge chain, or whose
-        capacity-sized edge list does not fit) -- the iteration is then launched eagerly, with one warning, instead of failing
-        inside the capture.  Networks without the method are taken at the caller's word (use_hip_graph=True)."""
-        ask = getattr(self.axl_network, "capture_safe", None)
-        if ask is None:
-            return True
-        safe = bool(ask(composition.X.shape[0], composition.X.shape[1], composition.X.device))
-        if not safe and not getattr(self, "_warned_not_capturable", False):
-            import warnings
+    def _capture_safe(self, composition: AXL) -> bool:
+        """Can the network's forward on this batch shape be captured (network_hooks.capture_safe)?  If not, the iteration is
+        launched eagerly, with one warning, instead of failing inside the capture."""
+        safe = hooks.capture_safe(self.axl_network, *composition.X.shape[:2], composition.X.device)
+        if not safe and not self._warned_not_capturable:
             warnings.warn("use_hip_graph=True, but the score network's forward on this batch shape needs a host "
                           "synchronisation: the sampler iteration is launched eagerly")
             self._warned_not_capturable = True
@@ -642,8 +580,7 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
         from ..models.score_networks.mlp_score_network import MLPScoreNetwork
         if not isinstance(self.axl_network, MLPScoreNetwork):
             raise MdxError("fused_score_network=True needs an MLPScoreNetwork; other networks use the per-step kernels")
-        if not getattr(self.noise_source, "device_rng", False) or self.record or type(self)._after_predictor is not \
-                LangevinGenerator._after_predictor:
+        if not self._device_rng or self.record or type(self)._after_predictor is not LangevinGenerator._after_predictor:
             raise MdxError("fused_score_network=True needs rng_mode='device', no recording and no repaint constraint")
         if self._mlp_pack is None or self._mlp_pack.device != torch.device(device):
             self._mlp_pack = kernels.MlpPack(self.axl_network, device)
@@ -665,16 +602,12 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
         """What a captured iteration depends on besides the tensors it reads: the batch's shape and device, the generator's
         settings that travel as kernel arguments, the network's parameters (their storage and version: the packed weight
         images are rebuilt when a parameter changes) and its arithmetic mode."""
-        net = self.axl_network
         settings = (self.number_of_corrector_steps, self.resampling_steps, self.atom_type_greedy_sampling,
                     self.one_atom_type_transition_per_step, self.atom_type_transition_in_corrector,
                     self.use_fixed_lattice_parameters, self.small_epsilon, self.num_classes)     # kernel arguments of the capture
         words = tuple(None if w is None else w.data_ptr() for w in (self._call_word, self._status))   # read by the captured kernels
-        # the force-field wrapper's cutoff and strength are kernel arguments too: their values, not the (mutable) object
-        force_field = getattr(net, "force_field_parameters", None)
-        return (tuple(start.X.shape), tuple(start.L.shape), str(start.X.device), getattr(net, "edge_chain_precision", None),
-                getattr(net, "first_layer_table", None), settings, words,
-                None if force_field is None else dataclasses.astuple(force_field),
+        net = self.axl_network
+        return (tuple(start.X.shape), tuple(start.L.shape), str(start.X.device), hooks.capture_key(net), settings, words,
                 tuple((p.data_ptr(), p._version) for p in net.parameters()))
 
     def _sample_with_graph(self, start: AXL, starting_step_index: int, ending_step_index: int) -> AXL:
@@ -683,7 +616,7 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
         (a capture costs about five iterations' time).  The result is a copy: the buffers belong to the graph."""
         key = self._graph_key(start)
         kept = self._buffers.get("graph_loop")
-        if kept is not None and getattr(kept, "key", None) == key:
+        if kept is not None and kept.key == key:
             loop = kept
             loop.reset(start, starting_step_index)
         else:
@@ -700,7 +633,7 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
             return
         word = int(self._status.item())
         self._status.zero_()
-        net_status = getattr(self.axl_network, "graph_status", None)
+        net_status = hooks.status_word(self.axl_network)
         if net_status is not None:
             # The network's report comes FIRST: an activation beyond the f16 range gives non-finite logits, which can leave
             # atoms MASKED -- a report that reaches this point (a caller stepping by hand: the loops handle it per iteration)
@@ -732,7 +665,6 @@ class IterationLoop:
     capture-safe (no host synchronisation).  Used by LangevinGenerator.sample and by bench.py."""
 
     def __init__(self, generator: LangevinGenerator, start: AXL, starting_step_index: int, use_graph: bool):
-        import weakref
         gen = generator
         # (a weak reference: the generator keeps its last loop alive in _buffers; a strong reference back would make the pair
         # cyclic garbage, and the collector -- not the last reference going away -- would decide WHEN the loop's hipGraph is
@@ -740,12 +672,14 @@ class IterationLoop:
         self.generator = weakref.proxy(generator)
         device = start.X.device
         gen._prepare(device)
-        assert getattr(gen.noise_source, "device_rng", False), "the device-resident loop needs rng_mode='device'"
+        assert gen._device_rng, "the device-resident loop needs rng_mode='device'"
         self.composition = AXL(A=start.A.clone(), X=start.X.clone(), L=start.L.clone())
         self.forces = torch.zeros_like(self.composition.X)
         self.d_index = torch.zeros(1, dtype=torch.int32, device=device)
         self.remaining = starting_step_index
         self.graph = None
+        self.key = None              # LangevinGenerator._graph_key of the state the graph was captured in (_sample_with_graph)
+        self._watch = None           # _watch_buffers
         if use_graph:
             comp = self.composition
             saved = AXL(A=comp.A.clone(), X=comp.X.clone(), L=comp.L.clone())
@@ -761,7 +695,7 @@ class IterationLoop:
             comp.X.copy_(saved.X)
             comp.L.copy_(saved.L)
             gen._status.zero_()
-            gen._clear_stale_range_report()      # (the warm-up ran the split-f16 network from an arbitrary state)
+            hooks.clear_reports(gen.axl_network)      # (the warm-up ran the split-f16 network from an arbitrary state)
             self.graph = torch.cuda.CUDAGraph()
             # Objects whose finaliser calls HIP must not be collected while the stream is capturing: an older loop's
             # torch.cuda.CUDAGraph (hipGraphExecDestroy).  It is released deterministically: the previous loop of this
@@ -774,7 +708,6 @@ class IterationLoop:
             # torch.cuda.graph() no longer collects garbage on entry (torch >= 2.9: only with
             # torch.compiler.config.force_cudagraph_gc): collect here, before the capture, and keep the collector off while
             # the stream is capturing -- nothing may run a finaliser that calls HIP in there.
-            import gc
             gc.collect()
             was_enabled = gc.isenabled()
             gc.disable()
@@ -808,7 +741,7 @@ class IterationLoop:
         """Run `iterations` sampler iterations on the current stream.  Asynchronous -- except when the score network runs
         split-f16 kernels (see _advance_watched): then the call returns once the last iteration's range report has been read."""
         assert iterations <= self.remaining, "cannot step past time index 0"
-        if self.generator._range_guarded():
+        if hooks.reports_watched(self.generator.axl_network):
             return self._advance_watched(iterations)
         for _ in range(iterations):
             self._one()
@@ -824,7 +757,7 @@ class IterationLoop:
     LAG = 2
 
     def _watch_buffers(self):
-        if getattr(self, "_watch", None) is None:
+        if self._watch is None:
             comp, slots = self.composition, self.LAG + 1
             self._watch = dict(
                 snapshots=[AXL(A=torch.empty_like(comp.A), X=torch.empty_like(comp.X), L=torch.empty_like(comp.L))
@@ -836,7 +769,7 @@ class IterationLoop:
     def _advance_watched(self, iterations: int):
         gen, w = self.generator, self._watch_buffers()
         net, slots = gen.axl_network, self.LAG + 1
-        gen._clear_stale_range_report()                 # (nothing of this call is queued yet: a set bit is someone else's)
+        hooks.clear_reports(net)                        # (nothing of this call is queued yet: a set bit is someone else's)
         first = self.remaining                          # iteration k of this call starts with `first - k` indices remaining
         k = checked = 0                                 # iterations queued / iterations whose report has been read
         while checked < iterations:
@@ -846,7 +779,7 @@ class IterationLoop:
                     dst.copy_(src)
                 assert self.remaining == first - k
                 self._one()
-                status = getattr(net, "graph_status", None)      # (the network creates its status word in its first forward)
+                status = hooks.status_word(net)                  # (the network creates its status word in its first forward)
                 if status is None:
                     w["words"][slot] = 0
                 else:
@@ -856,7 +789,7 @@ class IterationLoop:
                 continue
             slot = checked % slots
             w["events"][slot].synchronize()
-            report = int(w["words"][slot]) & gen.REPORTS
+            report = int(w["words"][slot]) & hooks.REPORTS
             if not report:
                 checked += 1
                 continue
@@ -866,16 +799,12 @@ class IterationLoop:
                 dst.copy_(src)
             self.remaining = first - checked
             kernels.index_set(self.d_index, self.remaining - 1)
-            status.bitwise_and_(~gen.REPORTS)
-            gen._status.zero_()                         # (bits the dropped iterations may have raised)
-            if report & STATUS_EGNN_F16_RANGE:
-                gen._count_fallback(self.remaining - 1)
+            hooks.clear_reports(net)                    # (those of the dropped iterations)
             if report & STATUS_EGNN_TABLE:
-                gen._count_table_fallback(self.remaining - 1)
                 # the captured iteration runs the table: from here on this loop launches eagerly (a later sample() call
                 # captures again -- first_layer_table is part of the graph's key)
                 self.graph = None
             # eager launches of the same iteration (exact-f32 kernels after an f16-range report)
-            gen._recompute(report, lambda: self._one(visits=1 + gen.resampling_steps))
+            gen._recover(report, self.remaining - 1, lambda: self._one(visits=1 + gen.resampling_steps))
             checked += 1
             k = checked

@@ -44,10 +44,25 @@ class ForceFieldAugmentedScoreNetwork(torch.nn.Module):
     def force_field_parameters(self) -> ForceFieldParameters:
         return self._force_field_parameters
 
-    # what the generators look for on a score network, passed through to the wrapped one (build-only attributes: the status
-    # word of its HIP kernels and the arithmetic of its fused MFMA kernels; the sampler's uniform-sigma hint and the EGNN's
-    # first-layer table).  An attribute the wrapped network lacks is absent here too, so a generator's hasattr / getattr
-    # default sees what it would see on the wrapped network.
+    # What the generators look for on a score network (generators/network_hooks.py is the contract).  The names below go
+    # straight through to the wrapped network, reads and sets alike.  One rule for all of them: a name the wrapped network
+    # lacks is absent here too (hasattr is false, and a set is dropped), so that the hooks' defaults for an absent name --
+    # None, "off", a no-op -- mean what they would mean on the wrapped network.  graph_status, check_status and capture_safe
+    # are written out below: they also answer for the pseudo-force kernel.
+    FORWARDED = ("edge_chain_precision", "sigma_uniform_hint", "first_layer_table", "adapt_f16_range",
+                 "begin_f16_range_fallback", "reset_f16_range")
+
+    def __getattr__(self, name):
+        if name in self.FORWARDED:
+            return getattr(self._score_network, name)
+        return super().__getattr__(name)
+
+    def __setattr__(self, name, value):
+        if name not in self.FORWARDED:
+            super().__setattr__(name, value)
+        elif hasattr(self._score_network, name):
+            setattr(self._score_network, name, value)
+
     @property
     def graph_status(self):
         """The status word of the last pseudo-force launch (the wrapped network's word when it has one), else the wrapped
@@ -69,52 +84,10 @@ class ForceFieldAugmentedScoreNetwork(torch.nn.Module):
         for w in held:
             neighbors._raise_if_cutoff_too_large(w)
 
-    @property
-    def edge_chain_precision(self):
-        return getattr(self._score_network, "edge_chain_precision", None)
-
-    @edge_chain_precision.setter
-    def edge_chain_precision(self, value):
-        if hasattr(self._score_network, "edge_chain_precision"):
-            self._score_network.edge_chain_precision = value
-
-    @property
-    def sigma_uniform_hint(self):
-        return self._score_network.sigma_uniform_hint
-
-    @sigma_uniform_hint.setter
-    def sigma_uniform_hint(self, value):
-        if hasattr(self._score_network, "sigma_uniform_hint"):
-            self._score_network.sigma_uniform_hint = value
-
-    @property
-    def first_layer_table(self):
-        return self._score_network.first_layer_table
-
-    @first_layer_table.setter
-    def first_layer_table(self, value):
-        if hasattr(self._score_network, "first_layer_table"):
-            self._score_network.first_layer_table = value
-
     def capture_safe(self, batch_size: int, number_of_atoms: int, device) -> bool:
         """The pseudo-force kernel needs no host synchronisation: the wrapped network's answer decides (True without one)."""
         ask = getattr(self._score_network, "capture_safe", None)
         return True if ask is None else bool(ask(batch_size, number_of_atoms, device))
-
-    def adapt_f16_range(self):
-        adapt = getattr(self._score_network, "adapt_f16_range", None)
-        if adapt is not None:
-            adapt()
-
-    def begin_f16_range_fallback(self):
-        begin = getattr(self._score_network, "begin_f16_range_fallback", None)
-        if begin is not None:
-            begin()
-
-    def reset_f16_range(self):
-        reset = getattr(self._score_network, "reset_f16_range", None)
-        if reset is not None:
-            reset()
 
     def forward(self, batch: Dict[AnyStr, torch.Tensor], conditional: Optional[bool] = None) -> AXL:
         raw = self._score_network(batch, conditional)

@@ -49,7 +49,7 @@ def main():
         gen._prepare(device)
         gen._begin_call(device)
         start = gen.initialize(batch, device)
-        use_graph = not args.eager and gen._network_is_capture_safe(start)
+        use_graph = not args.eager and gen._capture_safe(start)
         loop = IterationLoop(gen, start, T, use_graph=use_graph)
         bench.advance(loop, args.warmup, T)
         torch.cuda.synchronize(device)
