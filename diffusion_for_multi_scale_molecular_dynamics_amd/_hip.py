@@ -28,7 +28,8 @@ ABI_SYMBOLS = (
     "mdx_abi_version", "mdx_status_string", "mdx_noise_schedule_build", "mdx_index_set", "mdx_index_add",
     "mdx_fill_time_sigma", "mdx_relative_coordinates_update", "mdx_lattice_parameters_update",
     "mdx_relative_coordinates_update_dev", "mdx_lattice_parameters_update_dev",
-    "mdx_atom_types_update", "mdx_pc_step_update", "mdx_noise_relative_coordinates", "mdx_noise_atom_types", "mdx_noise_relative_coordinates_sigmas", "mdx_noise_atom_types_per_atom",
+    "mdx_atom_types_update", "mdx_pc_step_update", "mdx_adaptive_corrector_statistics", "mdx_adaptive_corrector_step_size",
+    "mdx_adaptive_corrector_update", "mdx_noise_relative_coordinates", "mdx_noise_atom_types", "mdx_noise_relative_coordinates_sigmas", "mdx_noise_atom_types_per_atom",
     "mdx_noise_lattice_parameters",
     "mdx_repaint_constrained_rows", "mdx_forward_diffusion_step", "mdx_radius_graph_count", "mdx_radius_graph_fill", "mdx_radius_graph_fill_capped", "mdx_egnn_radius_graph", "mdx_egnn_radius_graph_workspace_words", "mdx_force_field_pseudo_force", "mdx_mlp_forward",
     "mdx_mlp_pc_sample", "mdx_mlp_pc_sample_variant", "mdx_mlp_pc_sample_workspace_floats", "mdx_mlp_image_floats", "mdx_mlp_pack_image", "mdx_egnn_message_input", "mdx_egnn_coord_head", "mdx_segment_rows",
@@ -146,6 +147,14 @@ def _declare(L):
     L.mdx_atom_types_update.argtypes = [vp] * 7 + [i64, i32, i32, f32, i32, i32, vp, vp, vp]
     L.mdx_pc_step_update.restype = i32
     L.mdx_pc_step_update.argtypes = [C.POINTER(Schedule), i32, i32, vp, C.POINTER(PcFlags)] + [vp] * 10 + \
+        [Rng, i64, i32, i32, vp, vp, vp, vp, vp]
+    L.mdx_adaptive_corrector_statistics.restype = i32
+    L.mdx_adaptive_corrector_statistics.argtypes = [C.POINTER(Schedule), i32, vp, vp, vp, vp, vp, Rng, i64, i32, i32, i32, f32,
+                                                    f32, vp, vp, vp, vp]
+    L.mdx_adaptive_corrector_step_size.restype = i32
+    L.mdx_adaptive_corrector_step_size.argtypes = [C.POINTER(Schedule), i32, vp, vp, i32, i32, i32, f32, f32, vp, vp]
+    L.mdx_adaptive_corrector_update.restype = i32
+    L.mdx_adaptive_corrector_update.argtypes = [C.POINTER(Schedule), i32, i32, vp, C.POINTER(PcFlags)] + [vp] * 11 + \
         [Rng, i64, i32, i32, vp, vp, vp, vp, vp]
     L.mdx_noise_relative_coordinates.restype = i32
     L.mdx_noise_relative_coordinates.argtypes = [vp, vp, f32, i64, vp, vp]

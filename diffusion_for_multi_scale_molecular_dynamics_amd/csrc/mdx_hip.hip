@@ -7,6 +7,9 @@
 //   coords_update_kernel   P1  x' = wrap((x + w s / sigma) + n z)           flat, 16 B/lane
 //   pc_step_kernel         P2 (+P1 +P3) fused per-step update, one lane-group per structure,
 //                              wavefront-shuffle reductions over the atoms of a structure
+//   adaptive_stats_kernel      adaptive corrector: per-structure score / noise norms on pc_step_kernel's lane mapping,
+//   adaptive_totals_kernel     their binary64 batch sums (+ the step size) behind a launch boundary, fixed order, no atomics,
+//   adaptive_update_kernel     and the update with {eps, sqrt(2 eps), sigma} read from device words
 //   repaint_rows_kernel    R1  forward-noise + scatter of the constrained rows (F1 + F2 fused)
 //   radius_graph_kernel    N1  27-image radius graph, structure tile staged in LDS, one wavefront per source
 //                              row, ballot/scan ranked writes => edges come out sorted, no atomics
@@ -701,6 +704,24 @@ __device__ __forceinline__ void pc_update_structure(const PcArgs& p, const PcSte
 __device__ __forceinline__ const float* off(const float* p, int64_t o) { return p ? p + o : nullptr; }
 __device__ __forceinline__ float* off(float* p, int64_t o) { return p ? p + o : nullptr; }
 
+// The operands of structure b in global memory
+__device__ __forceinline__ PcView structure_view(const PcArgs& p, int64_t b)
+{
+    const int N = p.N, C = p.C, d = p.d;
+    PcView v;
+    const int64_t a0 = b * N;
+    v.a = p.a ? p.a + a0 : nullptr;
+    v.x = off(p.x, a0 * d); v.l = off(p.l, b * p.nl);
+    v.logits = off(p.logits, a0 * C); v.score_x = off(p.score_x, a0 * d); v.score_l = off(p.score_l, b * p.nl);
+    v.z_coord = off(p.z_coord, a0 * d); v.gumbel = off(p.gumbel, a0 * C); v.u = off(p.u, a0);
+    v.z_lat = off(p.z_lat, b * p.nl);
+    v.a_out = p.a_out ? p.a_out + a0 : nullptr;
+    v.x_out = off(p.x_out, a0 * d); v.l_out = off(p.l_out, b * p.nl); v.p_out = off(p.p_out, a0 * C);
+    v.item0 = a0;
+    v.b = b;
+    return v;
+}
+
 // G lanes cooperate on one structure; a 64-lane wavefront carries 64/G structures.
 // CSPEC > 0: number of classes (and d = 3) substituted as literals -- the class loops unroll to exactly C bodies and
 // the per-atom index arithmetic folds; CSPEC = 0 is the generic instantiation.  Same code, same arithmetic.
@@ -712,49 +733,272 @@ __global__ __launch_bounds__(kBlock) void pc_step_kernel(PcArgs p_in)
     const int lane = threadIdx.x & (G - 1);
     const int64_t groups_per_grid = ((int64_t)gridDim.x * blockDim.x) / G;
     const int64_t group0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
-    const int N = p.N, C = p.C, d = p.d;
     const PcStep st = make_step(p);
     for (int64_t b = group0; b < p.B; b += groups_per_grid) {
-        PcView v;
-        const int64_t a0 = b * N;
-        v.a = p.a ? p.a + a0 : nullptr;
-        v.x = off(p.x, a0 * d); v.l = off(p.l, b * p.nl);
-        v.logits = off(p.logits, a0 * C); v.score_x = off(p.score_x, a0 * d); v.score_l = off(p.score_l, b * p.nl);
-        v.z_coord = off(p.z_coord, a0 * d); v.gumbel = off(p.gumbel, a0 * C); v.u = off(p.u, a0);
-        v.z_lat = off(p.z_lat, b * p.nl);
-        v.a_out = p.a_out ? p.a_out + a0 : nullptr;
-        v.x_out = off(p.x_out, a0 * d); v.l_out = off(p.l_out, b * p.nl); v.p_out = off(p.p_out, a0 * C);
-        v.item0 = a0;
-        v.b = b;
+        const PcView v = structure_view(p, b);
         pc_update_structure<G>(p, st, v, lane, p.update_types);
     }
 }
 
-int launch_pc(const PcArgs& a, hipStream_t st)
+// lanes per structure: smallest power of two >= N, capped at the wavefront
+inline int lanes_per_structure(int N)
 {
-    // lanes per structure: smallest power of two >= N, capped at the wavefront
     int G = 1;
-    while (G < a.N && G < kWave) G <<= 1;
-    const int64_t threads = a.B * G;
-    int64_t blocks = cdiv(threads, kBlock);
+    while (G < N && G < kWave) G <<= 1;
+    return G;
+}
+
+inline dim3 structure_grid(int64_t B, int G)
+{
+    int64_t blocks = cdiv(B * G, kBlock);
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
-    dim3 grid((unsigned)blocks), block(kBlock);
+    return dim3((unsigned)blocks);
+}
+
+#define MDX_SWITCH_G(G, LAUNCH)                                                                              \
+    switch (G) {                                                                                             \
+        case 1: LAUNCH(1) break;                                                                             \
+        case 2: LAUNCH(2) break;                                                                             \
+        case 4: LAUNCH(4) break;                                                                             \
+        case 8: LAUNCH(8) break;                                                                             \
+        case 16: LAUNCH(16) break;                                                                           \
+        case 32: LAUNCH(32) break;                                                                           \
+        default: LAUNCH(64) break;                                                                           \
+    }
+
+int launch_pc(const PcArgs& a, hipStream_t st)
+{
+    const int G = lanes_per_structure(a.N);
+    const dim3 grid = structure_grid(a.B, G), block(kBlock);
     const int cspec = (a.d == 3 && (a.C == 2 || a.C == 3)) ? a.C : 0;
 #define MDX_LAUNCH_PC(GG)                                                                                   \
     if (cspec == 2) hipLaunchKernelGGL((pc_step_kernel<GG, 2>), grid, block, 0, st, a);                       \
     else if (cspec == 3) hipLaunchKernelGGL((pc_step_kernel<GG, 3>), grid, block, 0, st, a);                  \
     else hipLaunchKernelGGL((pc_step_kernel<GG, 0>), grid, block, 0, st, a);
-    switch (G) {
-        case 1: MDX_LAUNCH_PC(1) break;
-        case 2: MDX_LAUNCH_PC(2) break;
-        case 4: MDX_LAUNCH_PC(4) break;
-        case 8: MDX_LAUNCH_PC(8) break;
-        case 16: MDX_LAUNCH_PC(16) break;
-        case 32: MDX_LAUNCH_PC(32) break;
-        default: MDX_LAUNCH_PC(64) break;
-    }
+    MDX_SWITCH_G(G, MDX_LAUNCH_PC)
 #undef MDX_LAUNCH_PC
+    return launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Adaptive corrector (generators/adaptive_corrector.py:41-63,97-148): batch statistics, step size, update
+// ---------------------------------------------------------------------------------------------------------------
+// Sum over the G lanes of a group with the exchange pattern of group_and / group_argmax.  Binary32 addition is
+// commutative, so both lanes of a pair form the same bits at every stage: all lanes end with one value, and that value is a
+// function of the inputs alone (a fixed tree).
+template <int G, int O = G / 2>
+__device__ __forceinline__ float group_sum(float v)
+{
+    if constexpr (O > 0) {
+        v = group_sum<G, O / 2>(v);
+        v = v + partner<O>(v);
+    }
+    return v;
+}
+
+struct AdaptiveStatsArgs {
+    const float *score_x, *score_l, *z_coord, *z_lat;
+    mdx_rng_t rng;
+    int index_i;
+    const int32_t* d_index;
+    int64_t B;
+    int N, d, nl, fixed_lattice;
+    float* workspace;        // [B,4]: |s_X[b]|, sum_atoms |z_X[b,atom]|, |s_L[b]|, |z_L[b]|
+};
+
+// pc_step_kernel's lane mapping.  A NULL z pointer: the draw pc_update_structure makes for the same (index, offset), in registers.
+template <int G>
+__global__ __launch_bounds__(kBlock) void adaptive_stats_kernel(AdaptiveStatsArgs p)
+{
+    const int lane = threadIdx.x & (G - 1);
+    const int64_t groups_per_grid = ((int64_t)gridDim.x * blockDim.x) / G;
+    const int64_t group0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
+    const int N = p.N, d = p.d;
+    const int index = (p.d_index ? *p.d_index : 0) + p.index_i;
+    const uint32_t draw = (uint32_t)index * p.rng.draw_stride + p.rng.draw_offset;
+    const uint32_t k0 = (uint32_t)p.rng.seed, k1 = (uint32_t)(p.rng.seed >> 32), call8 = rng_call(p.rng) << 8;
+    // (the G lanes of a group share group0, so they run this loop together and every exchange partner is active)
+    for (int64_t b = group0; b < p.B; b += groups_per_grid) {
+        const int64_t a0 = b * N;
+        const float* sx = p.score_x + a0 * d;
+        const float* zx = p.z_coord ? p.z_coord + a0 * d : nullptr;
+        float ss = 0.0f, zn = 0.0f;
+        for (int n = lane; n < N; n += G) {
+            float z0 = 0.0f, z1 = 0.0f, z2 = 0.0f, z3 = 0.0f;
+            if (!zx) {
+                const u32x4 r = philox4x32_10((uint32_t)(a0 + n), call8, draw, MDX_TAG_COORD, k0, k1);
+                box_muller(r.v[0], r.v[1], z0, z1);
+                if (d > 2) box_muller(r.v[2], r.v[3], z2, z3);
+            }
+            float zz = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                if (k < d) {
+                    const int e = n * d + k;
+                    const float s = sx[e];
+                    const float zk = zx ? zx[e] : (k == 0 ? z0 : (k == 1 ? z1 : z2));
+                    ss = ss + s * s;
+                    zz = zz + zk * zk;
+                }
+            zn = zn + __builtin_sqrtf(zz);
+        }
+        ss = group_sum<G>(ss);
+        zn = group_sum<G>(zn);
+        float sl = 0.0f, zl = 0.0f;
+        if (!p.fixed_lattice) {
+            for (int k = lane; k < p.nl; k += G) {
+                float zk;
+                if (p.z_lat) zk = p.z_lat[b * p.nl + k];
+                else {
+                    const u32x4 r = philox4x32_10((uint32_t)b, call8 | (uint32_t)(k >> 2), draw, MDX_TAG_LATTICE, k0, k1);
+                    float z0, z1, z2, z3;
+                    box_muller(r.v[0], r.v[1], z0, z1);
+                    box_muller(r.v[2], r.v[3], z2, z3);
+                    const int kk = k & 3;
+                    zk = kk == 0 ? z0 : (kk == 1 ? z1 : (kk == 2 ? z2 : z3));
+                }
+                const float s = p.score_l[b * p.nl + k];
+                sl = sl + s * s;
+                zl = zl + zk * zk;
+            }
+            sl = group_sum<G>(sl);
+            zl = group_sum<G>(zl);
+        }
+        if (lane == 0) {
+            float* w = p.workspace + b * 4;
+            w[0] = __builtin_sqrtf(ss);
+            w[1] = zn;
+            w[2] = __builtin_sqrtf(sl);
+            w[3] = __builtin_sqrtf(zl);
+        }
+    }
+}
+
+struct AdaptiveStepArgs {
+    SchedDev sched;
+    int index_i;
+    const int32_t* d_index;
+    double atoms_pow;
+    float corrector_r, small_eps;
+    int fixed_lattice;
+    const double* totals;    // [8]: sum, count pairs of utils/batch_statistics.global_means
+    float* weights;          // [6]: {eps, sqrt(2 eps), sigma, eps_L, sqrt(2 eps_L), sigma_n}
+};
+
+// eps = 2 (r mean|z| / clip(mean|sigma s| / sigma, small_epsilon))^2 (:130-146): each mean rounded once to binary32, then
+// binary32 in the order of oracle/reference_sampler.py::OracleAdaptiveCorrectorGenerator._eps
+__device__ __forceinline__ float adaptive_eps(double sum_s, double count_s, double sum_z, double count_z, float sigma, float r,
+                                              float small_eps)
+{
+    const float mean_s = (float)(sum_s / count_s), mean_z = (float)(sum_z / count_z);
+    const float score_norm = mean_s / sigma;
+    const float ratio = (r * mean_z) / (score_norm > small_eps ? score_norm : small_eps);
+    return (2.0f * ratio) * ratio;
+}
+
+__device__ __forceinline__ void adaptive_step_size(const AdaptiveStepArgs& p, const double* t)
+{
+    const int index = (p.d_index ? *p.d_index : 0) + p.index_i;
+    const StepScalars sc = step_scalars(p.sched, MDX_CORRECTOR, index, p.atoms_pow);
+    const float eps = adaptive_eps(t[0], t[1], t[2], t[3], sc.sigma, p.corrector_r, p.small_eps);
+    const float eps_l = p.fixed_lattice ? 0.0f : adaptive_eps(t[4], t[5], t[6], t[7], sc.sigma_n, p.corrector_r, p.small_eps);
+    p.weights[0] = eps;
+    p.weights[1] = __builtin_sqrtf(2.0f * eps);
+    p.weights[2] = sc.sigma;
+    p.weights[3] = eps_l;
+    p.weights[4] = __builtin_sqrtf(2.0f * eps_l);
+    p.weights[5] = sc.sigma_n;
+}
+
+// ONE workgroup behind adaptive_stats_kernel's launch boundary: the [B,4] workspace summed in binary64 in a fixed order --
+// thread (slot, column) adds rows slot, slot + 64, ... in index order, then the 64 slots are folded in LDS, halves onto halves.
+// No atomics, no ticket: the bits do not depend on scheduling.  step.weights != NULL: the step size follows as the tail (the
+// statistics are not synchronised across ranks); else the caller all-reduces `totals` and launches adaptive_step_kernel.
+__global__ __launch_bounds__(kBlock) void adaptive_totals_kernel(const float* workspace, int64_t B, int N, double* totals,
+                                                                 AdaptiveStepArgs step)
+{
+    __shared__ double part[kBlock];
+    const int col = threadIdx.x & 3, slot = threadIdx.x >> 2;
+    double acc = 0.0;
+    for (int64_t b = slot; b < B; b += kBlock / 4) acc = acc + (double)workspace[b * 4 + col];
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    for (int half = kBlock / 8; half > 0; half >>= 1) {
+        if (slot < half) part[threadIdx.x] = part[threadIdx.x] + part[threadIdx.x + half * 4];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        double t[8];
+        for (int c = 0; c < 4; ++c) t[2 * c] = part[c];
+        t[1] = (double)B;
+        t[3] = (double)B * (double)N;
+        t[5] = (double)B;
+        t[7] = (double)B;
+        for (int c = 0; c < 8; ++c) totals[c] = t[c];
+        if (step.weights) adaptive_step_size(step, t);
+    }
+}
+
+__global__ void adaptive_step_kernel(AdaptiveStepArgs step)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        double t[8];
+        for (int c = 0; c < 8; ++c) t[c] = step.totals[c];
+        adaptive_step_size(step, t);
+    }
+}
+
+// The update on pc_update_structure (one arithmetic, the same in-register draws).  Predictor: atom types only, X and L are not
+// touched (:41-63).  Corrector: {w, n, sigma} of X and {w, n, sigma_n} of L come from `weights`, so the body runs once for the
+// coordinates (and the atom types, when the corrector updates them) and once for the lattice.
+template <int G>
+__global__ __launch_bounds__(kBlock) void adaptive_update_kernel(PcArgs p_in, const float* __restrict__ weights)
+{
+    PcArgs p = p_in;
+    const int lane = threadIdx.x & (G - 1);
+    const int64_t groups_per_grid = ((int64_t)gridDim.x * blockDim.x) / G;
+    const int64_t group0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
+    const bool corrector = p.mode == MDX_CORRECTOR;
+    PcStep st = make_step(p);
+    PcStep st_l = st;
+    PcArgs p_l = p;
+    if (corrector) {
+        st.sc.w = weights[0]; st.sc.n = weights[1]; st.sc.sigma = weights[2];
+        st_l.sc.w = weights[3]; st_l.sc.n = weights[4]; st_l.sc.sigma_n = weights[5];
+        p.do_coords = 1; p.do_lattice = 0;
+        p_l.do_coords = 0; p_l.do_lattice = 1;
+    } else {
+        p.do_coords = 0; p.do_lattice = 0;
+    }
+    for (int64_t b = group0; b < p.B; b += groups_per_grid) {
+        PcView v = structure_view(p, b);
+        pc_update_structure<G>(p, st, v, lane, p.update_types);
+        if (corrector) {
+            v.a = nullptr;
+            v.a_out = nullptr;
+            pc_update_structure<G>(p_l, st_l, v, lane, 0);
+        }
+    }
+}
+
+int launch_adaptive_stats(const AdaptiveStatsArgs& a, hipStream_t st)
+{
+    const int G = lanes_per_structure(a.N);
+    const dim3 grid = structure_grid(a.B, G), block(kBlock);
+#define MDX_LAUNCH_STATS(GG) hipLaunchKernelGGL((adaptive_stats_kernel<GG>), grid, block, 0, st, a);
+    MDX_SWITCH_G(G, MDX_LAUNCH_STATS)
+#undef MDX_LAUNCH_STATS
+    return launch_status();
+}
+
+int launch_adaptive_update(const PcArgs& a, const float* weights, hipStream_t st)
+{
+    const int G = lanes_per_structure(a.N);
+    const dim3 grid = structure_grid(a.B, G), block(kBlock);
+#define MDX_LAUNCH_UPDATE(GG) hipLaunchKernelGGL((adaptive_update_kernel<GG>), grid, block, 0, st, a, weights);
+    MDX_SWITCH_G(G, MDX_LAUNCH_UPDATE)
+#undef MDX_LAUNCH_UPDATE
     return launch_status();
 }
 
@@ -2680,6 +2924,105 @@ int mdx_pc_step_update(const mdx_schedule_t* sched_host, int mode, int index_i, 
     a.a_out = atom_types_out; a.x_out = x_out; a.l_out = l_out; a.p_out = nullptr;
     a.status = status;
     return launch_pc(a, as_stream(stream));
+}
+
+static AdaptiveStepArgs adaptive_step_args(const mdx_schedule_t* sched_host, int index_i, const int32_t* d_index,
+                                           int number_of_atoms, int spatial_dimension, int fixed_lattice, float corrector_r,
+                                           float small_epsilon, const double* totals, float* weights)
+{
+    AdaptiveStepArgs s{};
+    s.sched = to_dev(sched_host);
+    s.index_i = index_i; s.d_index = d_index;
+    s.atoms_pow = pow((double)number_of_atoms, 1.0 / (double)spatial_dimension);
+    s.corrector_r = corrector_r; s.small_eps = small_epsilon;
+    s.fixed_lattice = fixed_lattice;
+    s.totals = totals; s.weights = weights;
+    return s;
+}
+
+int mdx_adaptive_corrector_statistics(const mdx_schedule_t* sched_host, int index_i, const int32_t* d_index,
+                                      const float* score_x, const float* score_l, const float* z_coordinates,
+                                      const float* z_lattice_for_step_size, mdx_rng_t rng, int64_t batch, int number_of_atoms,
+                                      int spatial_dimension, int use_fixed_lattice_parameters, float corrector_r,
+                                      float small_epsilon, float* workspace, double* totals, float* weights,
+                                      mdx_stream_t stream)
+{
+    const int rc = check_index(sched_host, MDX_CORRECTOR, index_i, d_index);
+    if (rc != MDX_OK) return rc;
+    if (batch < 1 || number_of_atoms < 1 || spatial_dimension < 1 || spatial_dimension > 3) return MDX_ERR_INVALID_ARG;
+    if (!score_x || !workspace || !totals || (!use_fixed_lattice_parameters && !score_l)) return MDX_ERR_INVALID_ARG;
+    if ((int64_t)batch * number_of_atoms > 0xffffffffLL) return MDX_ERR_UNSUPPORTED;   // 32-bit Philox item index
+    AdaptiveStatsArgs a{};
+    a.score_x = score_x; a.score_l = score_l; a.z_coord = z_coordinates; a.z_lat = z_lattice_for_step_size;
+    a.rng = rng;
+    a.index_i = index_i; a.d_index = d_index;
+    a.B = batch; a.N = number_of_atoms; a.d = spatial_dimension;
+    a.nl = spatial_dimension * (spatial_dimension + 1) / 2;
+    a.fixed_lattice = use_fixed_lattice_parameters;
+    a.workspace = workspace;
+    const int rs = launch_adaptive_stats(a, as_stream(stream));
+    if (rs != MDX_OK) return rs;
+    hipLaunchKernelGGL(adaptive_totals_kernel, dim3(1), dim3(kBlock), 0, as_stream(stream), (const float*)workspace, batch,
+                       number_of_atoms, totals,
+                       adaptive_step_args(sched_host, index_i, d_index, number_of_atoms, spatial_dimension,
+                                          use_fixed_lattice_parameters, corrector_r, small_epsilon, totals, weights));
+    return launch_status();
+}
+
+int mdx_adaptive_corrector_step_size(const mdx_schedule_t* sched_host, int index_i, const int32_t* d_index,
+                                     const double* totals, int number_of_atoms, int spatial_dimension,
+                                     int use_fixed_lattice_parameters, float corrector_r, float small_epsilon, float* weights,
+                                     mdx_stream_t stream)
+{
+    const int rc = check_index(sched_host, MDX_CORRECTOR, index_i, d_index);
+    if (rc != MDX_OK) return rc;
+    if (number_of_atoms < 1 || spatial_dimension < 1 || spatial_dimension > 3 || !totals || !weights) return MDX_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(adaptive_step_kernel, dim3(1), dim3(1), 0, as_stream(stream),
+                       adaptive_step_args(sched_host, index_i, d_index, number_of_atoms, spatial_dimension,
+                                          use_fixed_lattice_parameters, corrector_r, small_epsilon, totals, weights));
+    return launch_status();
+}
+
+int mdx_adaptive_corrector_update(const mdx_schedule_t* sched_host, int mode, int index_i, const int32_t* d_index,
+                                  const mdx_pc_flags_t* f, const int64_t* atom_types, const float* x, const float* l,
+                                  const float* logits, const float* score_x, const float* score_l, const float* z_coordinates,
+                                  const float* gumbel, const float* u, const float* z_lattice, const float* weights,
+                                  mdx_rng_t rng, int64_t batch, int number_of_atoms, int spatial_dimension,
+                                  int64_t* atom_types_out, float* x_out, float* l_out, uint32_t* status, mdx_stream_t stream)
+{
+    const int rc = check_index(sched_host, mode, index_i, d_index);
+    if (rc != MDX_OK) return rc;
+    if (!f || batch < 0 || number_of_atoms < 1 || spatial_dimension < 1 || spatial_dimension > 3) return MDX_ERR_INVALID_ARG;
+    const int C = sched_host->num_classes;
+    if (C < 2) return MDX_ERR_INVALID_ARG;
+    if (C > MDX_MAX_CLASSES) return MDX_ERR_UNSUPPORTED;
+    if (batch == 0) return MDX_OK;
+    const int types = mode == MDX_PREDICTOR ? 1 : f->update_atom_types;
+    if (types && (!atom_types || !logits || !atom_types_out)) return MDX_ERR_INVALID_ARG;
+    if (mode == MDX_CORRECTOR) {
+        if (!weights || !x || !score_x || !x_out || !l || !l_out) return MDX_ERR_INVALID_ARG;
+        if (!f->use_fixed_lattice_parameters && !score_l) return MDX_ERR_INVALID_ARG;
+    }
+    if ((int64_t)batch * number_of_atoms > 0xffffffffLL) return MDX_ERR_UNSUPPORTED;   // 32-bit Philox item index
+    PcArgs a{};
+    a.sched = to_dev(sched_host);
+    a.use_tables = 1;
+    a.mode = mode; a.index_i = index_i; a.d_index = d_index;
+    a.atoms_pow = pow((double)number_of_atoms, 1.0 / (double)spatial_dimension);
+    a.greedy = f->atom_type_greedy_sampling; a.one_transition = f->one_atom_type_transition_per_step;
+    a.fixed_lattice = f->use_fixed_lattice_parameters; a.update_types = types;
+    a.small_eps = f->small_epsilon;
+    a.a = atom_types; a.logits = logits; a.gumbel = gumbel; a.u = u;
+    if (mode == MDX_CORRECTOR) {     // (the predictor passes X and L through: it reads and writes neither)
+        a.x = x; a.l = l; a.score_x = score_x; a.score_l = score_l; a.z_coord = z_coordinates; a.z_lat = z_lattice;
+        a.x_out = x_out; a.l_out = l_out;
+    }
+    a.rng = rng;
+    a.B = batch; a.N = number_of_atoms; a.d = spatial_dimension; a.C = C;
+    a.nl = spatial_dimension * (spatial_dimension + 1) / 2;
+    a.a_out = atom_types_out; a.p_out = nullptr;
+    a.status = status;
+    return launch_adaptive_update(a, weights, as_stream(stream));
 }
 
 int mdx_noise_relative_coordinates(const float* x0, const float* z, float sigma, int64_t count, float* out,

@@ -12,7 +12,7 @@ import torch
 from . import _hip
 from ._hip import Mlp, PcFlags, Rng, Schedule, check, lib, ptr, stream_handle
 
-F32, I64, I32 = torch.float32, torch.int64, torch.int32
+F32, F64, I64, I32 = torch.float32, torch.float64, torch.int64, torch.int32
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -162,6 +162,55 @@ def pc_step_update(sched: DeviceSchedule, mode: int, index_i: int, d_index: Opti
         ptr(atom_types_out, I64, "atom_types_out"), ptr(x_out, F32, "x_out"), ptr(l_out, F32, "l_out"),
         ptr(status, I32, "status"), stream_handle())
     check(rc, "mdx_pc_step_update")
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# adaptive corrector: batch statistics -> step size -> update (no host read in between)
+# ----------------------------------------------------------------------------------------------------------------
+def adaptive_corrector_statistics(sched: DeviceSchedule, index_i: int, d_index: Optional[torch.Tensor], score_x, score_l,
+                                  z_coordinates, z_lattice_for_step_size, rng: Rng, use_fixed_lattice_parameters: bool,
+                                  corrector_r: float, small_epsilon: float, workspace, totals, weights=None):
+    """Stage 1 (mdx_adaptive_corrector_statistics): per-structure norms into workspace float32 [B,4], their fixed-order
+    binary64 sums and counts into totals float64 [8]; with `weights` (float32 [6]) the step size follows in the same launch.
+    A None z is regenerated in registers from `rng`."""
+    B, N, d = score_x.shape
+    assert workspace.numel() == 4 * B and totals.numel() == 8 and (weights is None or weights.numel() == 6)
+    rc = lib().mdx_adaptive_corrector_statistics(
+        C.byref(sched.c_struct), int(index_i), ptr(d_index, I32, "d_index"), ptr(score_x, F32, "score_x"),
+        ptr(score_l, F32, "score_l"), ptr(z_coordinates, F32, "z_coordinates"),
+        ptr(z_lattice_for_step_size, F32, "z_lattice_for_step_size"), rng, B, N, d, int(bool(use_fixed_lattice_parameters)),
+        float(corrector_r), float(small_epsilon), ptr(workspace, F32, "workspace"), ptr(totals, F64, "totals"),
+        ptr(weights, F32, "weights"), stream_handle())
+    check(rc, "mdx_adaptive_corrector_statistics")
+
+
+def adaptive_corrector_step_size(sched: DeviceSchedule, index_i: int, d_index: Optional[torch.Tensor], totals,
+                                 number_of_atoms: int, spatial_dimension: int, use_fixed_lattice_parameters: bool,
+                                 corrector_r: float, small_epsilon: float, weights):
+    """Stage 2 (mdx_adaptive_corrector_step_size): weights float32 [6] = {eps, sqrt(2 eps), sigma, eps_L, sqrt(2 eps_L),
+    sigma_n} from totals float64 [8] (all-reduced by the caller when the batch is sharded)."""
+    assert totals.numel() == 8 and weights.numel() == 6
+    rc = lib().mdx_adaptive_corrector_step_size(
+        C.byref(sched.c_struct), int(index_i), ptr(d_index, I32, "d_index"), ptr(totals, F64, "totals"), int(number_of_atoms),
+        int(spatial_dimension), int(bool(use_fixed_lattice_parameters)), float(corrector_r), float(small_epsilon),
+        ptr(weights, F32, "weights"), stream_handle())
+    check(rc, "mdx_adaptive_corrector_step_size")
+
+
+def adaptive_corrector_update(sched: DeviceSchedule, mode: int, index_i: int, d_index: Optional[torch.Tensor], flags: PcFlags,
+                              atom_types, x, l, logits, score_x, score_l, z_coordinates, gumbel, u, z_lattice, weights,
+                              rng: Rng, atom_types_out, x_out, l_out, status: Optional[torch.Tensor]):
+    """Stage 3 (mdx_adaptive_corrector_update): pc_step_update's operands; corrector: scalars from `weights`; predictor: atom
+    types only."""
+    B, N, d = x.shape
+    rc = lib().mdx_adaptive_corrector_update(
+        C.byref(sched.c_struct), int(mode), int(index_i), ptr(d_index, I32, "d_index"), C.byref(flags),
+        ptr(atom_types, I64, "atom_types"), ptr(x, F32, "x"), ptr(l, F32, "l"), ptr(logits, F32, "logits"),
+        ptr(score_x, F32, "score_x"), ptr(score_l, F32, "score_l"), ptr(z_coordinates, F32, "z_coordinates"),
+        ptr(gumbel, F32, "gumbel"), ptr(u, F32, "u"), ptr(z_lattice, F32, "z_lattice"), ptr(weights, F32, "weights"), rng,
+        B, N, d, ptr(atom_types_out, I64, "atom_types_out"), ptr(x_out, F32, "x_out"), ptr(l_out, F32, "l_out"),
+        ptr(status, I32, "status"), stream_handle())
+    check(rc, "mdx_adaptive_corrector_update")
 
 
 # ----------------------------------------------------------------------------------------------------------------

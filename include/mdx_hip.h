@@ -173,6 +173,47 @@ MDX_API int mdx_pc_step_update(const mdx_schedule_t* sched_host, int mode, int i
                        int number_of_atoms, int spatial_dimension, int64_t* atom_types_out, float* x_out,
                        float* l_out, uint32_t* status, mdx_stream_t stream);
 
+/* AdaptiveCorrectorGenerator (generators/adaptive_corrector.py:41-63,97-148) in three stream-ordered stages with no host read;
+ * index = d_index ? *d_index + index_i : index_i as everywhere, the corrector's index rules (sigma_min at index 0).
+ *
+ * Stage 1, batch statistics of ONE corrector step (:125-136).  Per structure, on mdx_pc_step_update's lane mapping and with a
+ * fixed-order cross-lane sum: |s_X[b]| over atoms x space, sum over atoms of |z_X[b, atom]| (torch.linalg.norm(z, dim=-1)) and,
+ * with a free lattice, |s_L[b]| and |z_L[b]| -- binary32, correctly rounded sqrt -- stored to workspace [batch, 4] (floats).
+ * z_coordinates [B,N,d] / z_lattice_for_step_size [B,nl]: pre-drawn noise; NULL regenerates mdx_pc_step_update's draw of the
+ * same rng request in registers (same bits as mdx_rng_fill).  A second launch of ONE workgroup then sums the workspace in
+ * binary64 in a fixed order (no atomics: two calls on the same inputs give the same bits) into
+ *   totals[8] (doubles) = {sum|s_X|, B, sum|z_X|, B N, sum|s_L|, B, sum|z_L|, B}
+ * -- sums and counts, so ONE SUM all-reduce of `totals` over the ranks of a sharded batch reproduces the un-sharded means.
+ * weights (nullable, [6] floats): stage 2 runs as the tail of that launch (statistics not synchronised across ranks).
+ * sched_host, corrector_r, small_epsilon are read for that tail only. */
+MDX_API int mdx_adaptive_corrector_statistics(const mdx_schedule_t* sched_host, int index_i, const int32_t* d_index,
+                                      const float* score_x, const float* score_l, const float* z_coordinates,
+                                      const float* z_lattice_for_step_size, mdx_rng_t rng, int64_t batch,
+                                      int number_of_atoms, int spatial_dimension, int use_fixed_lattice_parameters,
+                                      float corrector_r, float small_epsilon, float* workspace, double* totals,
+                                      float* weights, mdx_stream_t stream);
+/* Stage 2, the step size (:137-146): each mean = (float)(sum / count), then in binary32
+ *   score_norm = mean_s / sigma;  ratio = (r mean_z) / max(score_norm, small_epsilon);  eps = (2 ratio) ratio
+ * weights[6] = {eps, sqrt(2 eps), sigma, eps_L, sqrt(2 eps_L), sigma_n}, sigma_n = sigma / N^(1/d); eps_L = 0 with a fixed
+ * lattice. */
+MDX_API int mdx_adaptive_corrector_step_size(const mdx_schedule_t* sched_host, int index_i, const int32_t* d_index,
+                                     const double* totals, int number_of_atoms, int spatial_dimension,
+                                     int use_fixed_lattice_parameters, float corrector_r, float small_epsilon,
+                                     float* weights, mdx_stream_t stream);
+/* Stage 3, the update, on mdx_pc_step_update's body (same operands, same in-register draws, outputs may alias inputs).
+ * mode MDX_CORRECTOR (:97-148): the score weight, noise weight and sigma of X and of L are read from `weights` and not from the
+ * tables.  z_lattice is the draw the UPDATE uses: the reference computes the lattice step size from one lattice draw and
+ * updates with the next, so stage 1 and stage 3 take their lattice noise separately.
+ * mode MDX_PREDICTOR (:41-63): atom types only -- x, l, the scores, x_out and l_out are neither read nor written; weights may be
+ * NULL; MDX_STATUS_MASK_AT_LAST_STEP is reported as by mdx_pc_step_update. */
+MDX_API int mdx_adaptive_corrector_update(const mdx_schedule_t* sched_host, int mode, int index_i, const int32_t* d_index,
+                                  const mdx_pc_flags_t* flags_host, const int64_t* atom_types, const float* x,
+                                  const float* l, const float* logits, const float* score_x, const float* score_l,
+                                  const float* z_coordinates, const float* gumbel, const float* u, const float* z_lattice,
+                                  const float* weights, mdx_rng_t rng, int64_t batch, int number_of_atoms,
+                                  int spatial_dimension, int64_t* atom_types_out, float* x_out, float* l_out,
+                                  uint32_t* status, mdx_stream_t stream);
+
 /* F1 -- RelativeCoordinatesNoiser.get_noisy_relative_coordinates_sample
  * (noisers/relative_coordinates_noiser.py:33-67): out = wrap(x0 + sigma*z). */
 MDX_API int mdx_noise_relative_coordinates(const float* x0, const float* z, float sigma, int64_t count, float* out,
