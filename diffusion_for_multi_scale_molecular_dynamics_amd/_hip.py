@@ -17,6 +17,7 @@ MDX_OK = 0
 MDX_PREDICTOR, MDX_CORRECTOR = 0, 1
 STATUS_CUTOFF_TOO_LARGE, STATUS_MASK_AT_LAST_STEP, STATUS_EGNN_F16_RANGE, STATUS_GRAPH_CAPACITY = 1, 2, 4, 8
 STATUS_EGNN_TABLE = 16
+STATUS_SW_NEIGHBOURS, STATUS_SW_ATOM_TYPE = 32, 64     # mdx_stillinger_weber_energy_forces
 EGNN_COORD_NORMALIZE, EGNN_COORD_TANH = 1, 2      # MDX_EGNN_COORD_* (coord_flags of mdx_egnn_node_gather / _coord_aggregate)
 EGNN_CHAIN_MAX_LAYERS = 16
 MAX_CLASSES = 8
@@ -36,6 +37,7 @@ ABI_SYMBOLS = (
     "mdx_egnn_chain_image_bytes", "mdx_egnn_chain_pack", "mdx_egnn_chain_adapt_activation_exponents", "mdx_egnn_edge_chain", "mdx_egnn_piece_rows", "mdx_segment_combine", "mdx_egnn_node_gather", "mdx_mlp_chain_rows", "mdx_egnn_coord_aggregate",
     "mdx_egnn_node_inputs", "mdx_egnn_scores", "mdx_egnn_outputs", "mdx_node_mlp_rows", "mdx_node_mlp_rows_split",
     "mdx_egnn_table_check", "mdx_egnn_table_gather", "mdx_rng_fill", "mdx_math_probe",
+    "mdx_stillinger_weber_workspace_doubles", "mdx_stillinger_weber_energy_forces",
 )
 MLP_MAX_HIDDEN = 8
 # options of mdx_mlp_pc_sample (include/mdx_hip.h)
@@ -183,6 +185,10 @@ def _declare(L):
     L.mdx_egnn_radius_graph_workspace_words.argtypes = [i64, i32]
     L.mdx_force_field_pseudo_force.restype = i32
     L.mdx_force_field_pseudo_force.argtypes = [vp, vp, i32, f32, f32, f32, i64, i32, vp, vp, vp, vp]
+    L.mdx_stillinger_weber_workspace_doubles.restype = i64
+    L.mdx_stillinger_weber_workspace_doubles.argtypes = [i64, i32, i32]
+    L.mdx_stillinger_weber_energy_forces.restype = i32
+    L.mdx_stillinger_weber_energy_forces.argtypes = [vp, vp, i32, vp, vp, i32, i64, i32, i32, vp, i64, vp, vp, vp, vp]
     L.mdx_mlp_forward.restype = i32
     L.mdx_mlp_forward.argtypes = [C.POINTER(Mlp), vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
     L.mdx_mlp_pc_sample.restype = i32

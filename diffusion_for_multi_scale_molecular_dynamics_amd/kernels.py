@@ -384,6 +384,63 @@ def force_field_pseudo_force(relative_coordinates, lattice_parameters, clip_min:
     return out
 
 
+class StillingerWeberNeighbourCapacityError(_hip.MdxError):
+    """MDX_STATUS_SW_NEIGHBOURS: an atom has more neighbours than the call's neighbour capacity; call again with a larger one."""
+
+
+SW_NEIGHBOUR_CAPACITY = 64         # slots per atom of the neighbour lists (diamond Si has 4 inside a sigma, a dense random gas ~45)
+
+
+def stillinger_weber_energy_forces(relative_coordinates, lattice_parameters, atom_types, parameter_table, with_forces: bool = True,
+                                   neighbour_capacity: int = SW_NEIGHBOUR_CAPACITY, status: Optional[torch.Tensor] = None,
+                                   workspace: Optional[torch.Tensor] = None):
+    """Stillinger-Weber energies f64 [B] (eV) and Cartesian forces f64 [B,N,3] (eV/Angstrom; None without `with_forces`) of
+    relative coordinates f32 [B,N,3] in the orthogonal boxes lattice_parameters[:, :3] (f32 [B, >=3]) with atom types int64 [B,N]
+    and the device table f64 [n,n,n,10] of read_stillinger_weber_coefficients (mdx_stillinger_weber_energy_forces): one launch,
+    binary64, gathered forces, the same bits on every launch.  Without `status` the device status word is read ONCE after the
+    call and a side below the largest cutoff, an atom type outside the table (MASK included) or a neighbour overflow raises;
+    with a caller's `status` (int32 [1]) nothing is read on the host -- the call can be captured -- and the caller inspects the
+    bits (the affected structures hold NaNs).  `workspace`: f64, reused when large enough."""
+    for name, t in (("relative_coordinates", relative_coordinates), ("lattice_parameters", lattice_parameters),
+                    ("atom_types", atom_types), ("parameter_table", parameter_table)):
+        if not t.is_cuda:
+            raise _hip.MdxError(f"{name} lives on {t.device}: the Stillinger-Weber kernel runs on the GPU only (no CPU fallback)")
+    B, N, d = relative_coordinates.shape
+    if d != 3:
+        raise _hip.MdxError(f"Stillinger-Weber: spatial dimension 3 only, got {d}")
+    assert lattice_parameters.dim() == 2 and lattice_parameters.shape[0] == B and lattice_parameters.shape[1] >= 3
+    assert atom_types.shape == (B, N)
+    n = parameter_table.shape[0]
+    assert parameter_table.shape == (n, n, n, 10), "the parameter table is [n_types, n_types, n_types, 10]"
+    dev = relative_coordinates.device
+    words = int(lib().mdx_stillinger_weber_workspace_doubles(B, N, int(neighbour_capacity)))
+    if workspace is None or workspace.numel() < words:
+        workspace = torch.empty(max(words, 1), dtype=F64, device=dev)
+    energies = torch.empty(B, dtype=F64, device=dev)
+    forces = torch.empty(B, N, 3, dtype=F64, device=dev) if with_forces else None
+    own_status = status is None
+    if own_status:
+        status = torch.zeros(1, dtype=I32, device=dev)
+    check(lib().mdx_stillinger_weber_energy_forces(ptr(relative_coordinates, F32, "relative_coordinates"),
+                                                   ptr(lattice_parameters, F32, "lattice_parameters"), lattice_parameters.shape[1],
+                                                   ptr(atom_types, I64, "atom_types"), ptr(parameter_table, F64, "parameter_table"),
+                                                   n, B, N, int(neighbour_capacity), ptr(workspace, F64, "workspace"),
+                                                   workspace.numel(), ptr(energies, F64, "energies"), ptr(forces, F64, "forces"),
+                                                   ptr(status, I32, "status"), stream_handle()),
+          "mdx_stillinger_weber_energy_forces")
+    if own_status:
+        bits = int(status.item())
+        if bits & _hip.STATUS_SW_ATOM_TYPE:
+            raise _hip.MdxError(f"Stillinger-Weber: an atom type lies outside the parameter table's {n} types (a MASK among them?)")
+        if bits & _hip.STATUS_CUTOFF_TOO_LARGE:
+            raise _hip.MdxError("Stillinger-Weber: a box side is shorter than the largest cutoff a*sigma of the table: the 27-image "
+                                "sweep would miss neighbours (MDX_STATUS_CUTOFF_TOO_LARGE)")
+        if bits & _hip.STATUS_SW_NEIGHBOURS:
+            raise StillingerWeberNeighbourCapacityError(
+                f"Stillinger-Weber: an atom has more than neighbour_capacity={neighbour_capacity} neighbours (MDX_STATUS_SW_NEIGHBOURS)")
+    return energies, forces
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # fused MLP score network
 # ----------------------------------------------------------------------------------------------------------------

@@ -9,7 +9,10 @@ Differences, all additive:
     score_network:` block in the config, or is randomly initialised with `--random_init_seed` (synthetic benchmarks);
   * under `torchrun` (one process per GPU) the sub-batches are sharded over the ranks and gathered once (RCCL);
     rank 0 writes the files (`trajectories.pt` holds every rank's recorded sub-batches, in sub-batch order);
-  * LAMMPS energies (`oracle:`) and Orion reporting are outside the hot path and are not evaluated.
+  * `oracle: {name: stillinger_weber, sw_coeff_filename: <a LAMMPS .sw file, absolute or relative to the configuration>}` writes
+    `energies.pt` (the Stillinger-Weber energy of every sample, CPU float64, as the reference's :243-251) from a HIP kernel;
+    `name: lammps` is reported as out of scope (no LAMMPS here: samples.pt is written, energies.pt is not), Orion reporting
+    is absent.
 """
 import argparse
 import logging
@@ -31,7 +34,10 @@ from .models.score_networks.score_network import ScoreNetwork
 from .data.element_types import ElementTypes
 from .models.score_networks.score_network_factory import create_score_network, create_score_network_parameters
 from .noise_schedulers.noise_parameters import NoiseParameters
+from .namespace import AXL, AXL_COMPOSITION
 from .sampling.diffusion_sampling import create_batch_of_samples_sharded
+from .utils.structure_utils import (StillingerWeberParameters, compute_stillinger_weber_energies_and_forces,
+                                    read_stillinger_weber_coefficients)
 
 logger = logging.getLogger(__name__)
 
@@ -124,9 +130,7 @@ def main(args: Optional[Any] = None, axl_network: Optional[ScoreNetwork] = None)
         logger.info("Sampling in the reference's mode (draws from torch's CPU generator in the reference's order, uploaded every step, "
                     "eager launches: reproduces the reference's run for a given torch.manual_seed).  `rng_mode: device` and "
                     "`use_hip_graph: true` in the `sampling:` block select the throughput modes (INTEGRATION.md).")
-    if "oracle" in hyper_params:
-        logger.warning("The configuration has an `oracle:` block: the energy oracle (LAMMPS) is outside this package's scope; "
-                       "samples.pt is written, energies.pt is not.")
+    oracle_parameters = oracle_parameters_of(hyper_params, args.config)
     if axl_network is None:
         if args.random_init_seed is not None:
             torch.manual_seed(args.random_init_seed)
@@ -156,16 +160,39 @@ def main(args: Optional[Any] = None, axl_network: Optional[ScoreNetwork] = None)
     generator = instantiate_generator(sampling_parameters=sampling_parameters, noise_parameters=noise_parameters,
                                       axl_network=axl_network, trajectory_initializer=trajectory_initializer,
                                       sampling_constraints=sampling_constraints)
-    create_samples_and_write_to_disk(generator, sampling_parameters, None, device, args.output, rank,
+    create_samples_and_write_to_disk(generator, sampling_parameters, oracle_parameters, device, args.output, rank,
                                      for_reference=args.reference_pickles)
+
+
+def oracle_parameters_of(hyper_params: Dict[AnyStr, Any], config_path) -> Optional[StillingerWeberParameters]:
+    """The `oracle:` block (:141-147).  `name: stillinger_weber` needs the configuration's `elements` and a coefficient file
+    that exists and parses (absolute, or relative to the configuration file): anything else is refused HERE, before sampling.
+    Every other oracle (`lammps`) is reported as out of scope: None."""
+    if "oracle" not in hyper_params:
+        return None
+    block = dict(hyper_params["oracle"])
+    if block.get("name") != "stillinger_weber":
+        logger.warning("The configuration has an `oracle:` block: the energy oracle (LAMMPS) is outside this package's scope; "
+                       "samples.pt is written, energies.pt is not.")
+        return None
+    assert "elements" in hyper_params, "elements are needed to define the energy oracle."
+    assert "sw_coeff_filename" in block, "`oracle: name: stillinger_weber` needs `sw_coeff_filename`, a LAMMPS .sw file"
+    path = Path(block["sw_coeff_filename"])
+    if not path.is_absolute():
+        path = Path(config_path).resolve().parent / path
+    parameters = StillingerWeberParameters(**dict(block, sw_coeff_filename=str(path)), elements=hyper_params["elements"])
+    read_stillinger_weber_coefficients(parameters.sw_coeff_filename, parameters.elements)       # refusals come now
+    return parameters
 
 
 def create_samples_and_write_to_disk(generator, sampling_parameters, oracle_parameters, device, output_path, rank: int = 0,
                                      for_reference: bool = False):
-    """:208-270.  oracle_parameters: the reference's third argument (an energy oracle to evaluate the samples with, LAMMPS):
-    outside this package's scope -- anything but None is refused; Orion reporting likewise absent."""
-    if oracle_parameters is not None:
-        raise NotImplementedError("energy oracles (LAMMPS) are outside this package's scope: pass oracle_parameters=None")
+    """:208-270.  oracle_parameters: the reference's third argument, the energy oracle to evaluate the samples with: None or
+    StillingerWeberParameters (rank 0 then writes energies.pt); LAMMPS and anything else is outside this package's scope and
+    refused; Orion reporting likewise absent."""
+    if oracle_parameters is not None and not isinstance(oracle_parameters, StillingerWeberParameters):
+        raise NotImplementedError("energy oracles other than StillingerWeberParameters (LAMMPS) are outside this package's scope: "
+                                  "pass oracle_parameters=None")
     logger.info("Generating samples...")
     with torch.no_grad():
         samples_batch = create_batch_of_samples_sharded(generator=generator, sampling_parameters=sampling_parameters,
@@ -187,6 +214,16 @@ def create_samples_and_write_to_disk(generator, sampling_parameters, oracle_para
     else:
         with open(output_directory / "samples.pt", "wb") as fd:
             torch.save(samples_batch, fd)
+    if oracle_parameters is not None:
+        logger.info("Compute energy from Oracle...")
+        axl = samples_batch[AXL_COMPOSITION]
+        chunks = []
+        for start in range(0, axl.X.shape[0], sampling_parameters.sample_batchsize):
+            chunk = {AXL_COMPOSITION: AXL(*(t[start:start + sampling_parameters.sample_batchsize] for t in axl))}
+            chunks.append(compute_stillinger_weber_energies_and_forces(chunk, oracle_parameters)[0].cpu())
+        logger.info("Writing energies to disk...")
+        with open(output_directory / "energies.pt", "wb") as fd:
+            torch.save(torch.cat(chunks), fd)
     logger.info("Done!")
 
 

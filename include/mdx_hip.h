@@ -45,6 +45,10 @@ extern "C" {
 #define MDX_STATUS_EGNN_TABLE 16u        /* mdx_egnn_table_check / _gather: the first layer's distance table does not
                                             stand in for the per-edge chain (interpolation error, sigma not uniform,
                                             a distance or class outside the table) -- recompute on the per-edge chain */
+#define MDX_STATUS_SW_NEIGHBOURS 32u     /* mdx_stillinger_weber_energy_forces: an atom has more neighbours than the
+                                            caller's neighbour capacity (its structure's results are NaN, not truncated) */
+#define MDX_STATUS_SW_ATOM_TYPE 64u      /* mdx_stillinger_weber_energy_forces: an atom type outside the parameter table
+                                            (MASK included); its structure's results are NaN                           */
 
 #define MDX_MAX_CLASSES 8      /* C supported by the fused atom-type kernels */
 #define MDX_PREDICTOR 0
@@ -324,6 +328,34 @@ MDX_API int mdx_force_field_pseudo_force(const float* relative_coordinates, cons
                                          float clip_min, float radial_cutoff, float two_strength, int64_t batch,
                                          int number_of_atoms, const float* score_in, float* out, uint32_t* status,
                                          mdx_stream_t stream);
+
+/* Stillinger-Weber energies and forces (LAMMPS `pair_style sw`, metal units): what the reference's energy oracle obtains from
+ * LAMMPS for every sample (oracle/lammps_energy_oracle.py:56-158, called through oracle/energy_oracle.py:44-131), evaluated
+ * from the closed formula over all periodic images of an ORTHOGONAL box:
+ *   E    = sum_i sum_{j>i} phi2(r_ij) + sum_i sum_{j != i} sum_{k>j} phi3(r_ij, r_ik, theta_jik)
+ *   phi2 = A eps [B (sigma/r)^p - (sigma/r)^q] exp(sigma / (r - a sigma))                 r < a sigma, entry (ti, tj, tj)
+ *   phi3 = lambda eps (cos theta - cos theta0)^2 exp(g_ij s_ij / (r_ij - a_ij s_ij)) exp(g_ik s_ik / (r_ik - a_ik s_ik))
+ *          lambda, eps, cos theta0 of entry (ti, tj, tk); sigma, a, gamma of the ij leg of (ti, tj, tj), of the ik leg of
+ *          (ti, tk, tk); each leg inside its own cutoff
+ * relative_coordinates f32 [batch, N, 3], expected in [0, 1) as the sampler leaves them (the sweep covers the images -1, 0, +1 of
+ * the coordinates as given: it does not wrap them); lattice_parameters f32 [batch, lattice_stride], the first three the box sides (the
+ * rest is not read); atom_types int64 [batch, N]; parameter_table: DEVICE double [n_types^3][10], entry (ti, tj, tk) =
+ * {eps, sigma, a, lambda, gamma, cos theta0, A, B, p, q}.  energies: double [batch] (eV); forces (nullable): double
+ * [batch, N, 3], Cartesian (eV / Angstrom).  Binary64 throughout, from the binary32 inputs promoted once (position =
+ * (double)relative * (double)side).  No float atomics: every force is gathered and every sum has a fixed order, so the bits
+ * do not depend on the launch or on the rest of the batch.  One launch, no host read.
+ * The +-1 image sweep is complete only while every side >= the largest a sigma of the table: a structure with a shorter (or
+ * NaN) side gets NaN energy and forces and MDX_STATUS_CUTOFF_TOO_LARGE.  An atom type outside [0, n_types) gives NaNs and
+ * MDX_STATUS_SW_ATOM_TYPE; an atom with more than neighbour_capacity neighbours NaNs and MDX_STATUS_SW_NEIGHBOURS (never a
+ * truncated sum).  Non-finite coordinates give NaNs.  status is nullable.
+ * workspace: caller-owned, at least mdx_stillinger_weber_workspace_doubles(batch, N, neighbour_capacity) doubles (the neighbour
+ * lists: 4 doubles per slot); workspace_doubles is its size.  N <= 1024 and n_types <= 8, else MDX_ERR_UNSUPPORTED. */
+MDX_API int64_t mdx_stillinger_weber_workspace_doubles(int64_t batch, int number_of_atoms, int neighbour_capacity);
+MDX_API int mdx_stillinger_weber_energy_forces(const float* relative_coordinates, const float* lattice_parameters,
+                                               int lattice_stride, const int64_t* atom_types, const double* parameter_table,
+                                               int n_types, int64_t batch, int number_of_atoms, int neighbour_capacity,
+                                               double* workspace, int64_t workspace_doubles, double* energies, double* forces,
+                                               uint32_t* status, mdx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Fused score network: the reference's MLPScoreNetwork (models/score_networks/mlp_score_network.py:54-370,
