@@ -96,7 +96,7 @@ class EgnnChain(C.Structure):
 
 
 def build(force=False):
-    """Compile csrc/mdx_hip.hip for gfx950 with hipcc (cross-compiles without a GPU)."""
+    """Compile every unit of csrc/ into libmdx_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".hpp", ".h")) or f == "Makefile"]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "mdx_hip.h"))
     stale = not os.path.exists(LIB_PATH) or any(os.path.getmtime(LIB_PATH) < os.path.getmtime(s) for s in srcs)

@@ -11,10 +11,15 @@
 #include <stdint.h>
 
 #include "../../include/mdx_hip.h"
+#include "mdx_launch.hpp"
+
+// (named, not `using namespace`: this unit has a wave_sum of its own, on DPP adds)
+using mdx::as_stream;
+using mdx::kBlock;
+using mdx::kWave;
+using mdx::launch_status;
 
 namespace {
-
-constexpr int kBlock = 256;
 
 __device__ __forceinline__ float silu_fast(float a) { return a / (1.0f + __expf(-a)); }
 
@@ -225,7 +230,6 @@ __device__ __forceinline__ float wave_sum(float v)
 }
 
 constexpr int kMaxClasses = 8;
-constexpr int kWaveSize = 64;
 
 __global__ __launch_bounds__(kBlock) void egnn_outputs_kernel(const float* __restrict__ z, const float* __restrict__ x_hat,
                                                               const float* __restrict__ k_vectors, int n_k,
@@ -237,16 +241,16 @@ __global__ __launch_bounds__(kBlock) void egnn_outputs_kernel(const float* __res
 {
     const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, n_threads = (int64_t)gridDim.x * blockDim.x;
     for (int64_t t = tid; t < n_zero; t += n_threads) zero_out[t] = 0.0f;
-    const int lane = threadIdx.x % kWaveSize;
+    const int lane = threadIdx.x % kWave;
     const int quads = H >> 2;
     // kNodesPerWave nodes per wavefront and pass: their rows of h, and the score operands of 3 lanes per node, are all
     // requested before anything is reduced (one row per pass left most of the launch waiting on a single 1 KB read)
     constexpr int kNodesPerWave = 4;
-    const int64_t n_waves = n_threads / kWaveSize;
-    for (int64_t node0 = (tid / kWaveSize) * kNodesPerWave; node0 < n_nodes; node0 += n_waves * kNodesPerWave) {
+    const int64_t n_waves = n_threads / kWave;
+    for (int64_t node0 = (tid / kWave) * kNodesPerWave; node0 < n_nodes; node0 += n_waves * kNodesPerWave) {
         float acc = 0.0f;
-        const int score_node = (lane - (kWaveSize - 3 * kNodesPerWave)) / 3, alpha = (lane - (kWaveSize - 3 * kNodesPerWave)) % 3;
-        const bool scores_lane = lane >= kWaveSize - 3 * kNodesPerWave && node0 + score_node < n_nodes;
+        const int score_node = (lane - (kWave - 3 * kNodesPerWave)) / 3, alpha = (lane - (kWave - 3 * kNodesPerWave)) % 3;
+        const bool scores_lane = lane >= kWave - 3 * kNodesPerWave && node0 + score_node < n_nodes;
         if (scores_lane) {
             const float* zi = z + (node0 + score_node) * 2 * n_k;
             const float* xi = x_hat + (node0 + score_node) * 2 * n_k;
@@ -260,7 +264,7 @@ __global__ __launch_bounds__(kBlock) void egnn_outputs_kernel(const float* __res
         for (int m = 0; m < kNodesPerWave; ++m)
 #pragma unroll
             for (int c = 0; c < kMaxClasses; ++c) part[m][c] = 0.0f;
-        for (int q = lane; q < quads; q += kWaveSize) {
+        for (int q = lane; q < quads; q += kWave) {
             float4 hv[kNodesPerWave];
 #pragma unroll
             for (int m = 0; m < kNodesPerWave; ++m)
@@ -293,7 +297,6 @@ __global__ __launch_bounds__(kBlock) void egnn_outputs_kernel(const float* __res
 // Segment kernels on the radius graph's sorted edge list (edges of node i are rows [offset_i, offset_i + degree_i)):
 // one wavefront per node, a row of H floats read as 16-byte lane loads (H = 256: one fully coalesced 1-KB row per
 // instruction), four rows in flight.  No atomics; the summation order is fixed (edge order), run-to-run deterministic.
-constexpr int kWave = 64;
 
 // trans[i, :] = scale_i * sum_e coord_diff[e, :] * (hidden[e, :] . w)      -- last layer of E_GCL.coord_model
 // (Linear(H, 1, bias=False), models/egnn.py:162-200) + the multiplication with coord_diff + the segment sum/mean
@@ -320,8 +323,7 @@ __global__ __launch_bounds__(kBlock) void egnn_coord_head_kernel(const float* __
             return part;
         };
         auto finish = [&](int64_t e, float part) {
-#pragma unroll
-            for (int o = kWave / 2; o > 0; o >>= 1) part += __shfl_xor(part, o, kWave);
+            part = mdx::wave_sum(part);                     // the xor butterfly, not the DPP sum above
             if (lane < d) acc += coord_diff[e * d + lane] * part;
         };
         int64_t e = e0;
@@ -372,9 +374,9 @@ int mdx_egnn_message_input(const float* node_proj, const int64_t* edges, const f
     if (!node_proj || !edges || !radial || !bias || !w_radial || !out) return MDX_ERR_INVALID_ARG;
     int64_t blocks = (n_edges * (H >> 2) + kBlock - 1) / kBlock;
     if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(egnn_message_input_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(egnn_message_input_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream),
                        node_proj, edges, radial, bias, w_radial, n_edges, H, silu, out);
-    return hipGetLastError() == hipSuccess ? MDX_OK : MDX_ERR_HIP;
+    return launch_status();
 }
 
 static unsigned node_grid(int64_t n_nodes)
@@ -400,17 +402,17 @@ int mdx_egnn_node_inputs(const float* x, const float* k_vectors, int n_k, const 
         int64_t blocks = (n_nodes + 15) / 16;
         if (blocks > 2048) blocks = 2048;
         hipLaunchKernelGGL(egnn_node_inputs_rows_kernel, dim3((unsigned)blocks), dim3(kBlock), table_bytes,
-                           reinterpret_cast<hipStream_t>(stream), x, k_vectors, n_k, sigma, atoms_per_structure, atom_types,
+                           as_stream(stream), x, k_vectors, n_k, sigma, atoms_per_structure, atom_types,
                            emb_weight, emb_bias, n_features, H, n_nodes, z_out, h_out, second_weight, second_bias, second_width,
                            second_out);
-        return hipGetLastError() == hipSuccess ? MDX_OK : MDX_ERR_HIP;
+        return launch_status();
     }
     int64_t blocks = (n_nodes * H + kBlock - 1) / kBlock;
     if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(egnn_node_inputs_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream), x,
+    hipLaunchKernelGGL(egnn_node_inputs_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), x,
                        k_vectors, n_k, sigma, atoms_per_structure, atom_types, emb_weight, emb_bias, n_features, H, n_nodes,
                        z_out, h_out, second_weight, second_bias, second_width, second_out);
-    return hipGetLastError() == hipSuccess ? MDX_OK : MDX_ERR_HIP;
+    return launch_status();
 }
 
 int mdx_egnn_scores(const float* z, const float* x_hat, const float* k_vectors, int n_k, int64_t n_nodes, float* scores_out,
@@ -421,9 +423,9 @@ int mdx_egnn_scores(const float* z, const float* x_hat, const float* k_vectors, 
     if (!z || !x_hat || !k_vectors || !scores_out) return MDX_ERR_INVALID_ARG;
     int64_t blocks = (n_nodes * 3 + kBlock - 1) / kBlock;
     if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(egnn_scores_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream), z, x_hat,
+    hipLaunchKernelGGL(egnn_scores_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), z, x_hat,
                        k_vectors, n_k, n_nodes, scores_out);
-    return hipGetLastError() == hipSuccess ? MDX_OK : MDX_ERR_HIP;
+    return launch_status();
 }
 
 int mdx_egnn_outputs(const float* z, const float* x_hat, const float* k_vectors, int n_k, const float* h,
@@ -437,10 +439,10 @@ int mdx_egnn_outputs(const float* z, const float* x_hat, const float* k_vectors,
     if (n_nodes == 0 && n_zero == 0) return MDX_OK;
     if (n_nodes > 0 && (!z || !x_hat || !k_vectors || !h || !class_weight || !class_bias || !scores_out || !logits_out))
         return MDX_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(egnn_outputs_kernel, dim3(node_grid((n_nodes + 3) / 4)), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream), z,
+    hipLaunchKernelGGL(egnn_outputs_kernel, dim3(node_grid((n_nodes + 3) / 4)), dim3(kBlock), 0, as_stream(stream), z,
                        x_hat, k_vectors, n_k, h, class_weight, class_bias, H, num_classes, mask_class, n_nodes, scores_out,
                        logits_out, zero_out, n_zero);
-    return hipGetLastError() == hipSuccess ? MDX_OK : MDX_ERR_HIP;
+    return launch_status();
 }
 
 int mdx_egnn_coord_head(const float* hidden, const float* w_out, const float* coord_diff, const int64_t* offsets,
@@ -451,9 +453,9 @@ int mdx_egnn_coord_head(const float* hidden, const float* w_out, const float* co
     if ((H & 3) || spatial_dimension > kWave) return MDX_ERR_UNSUPPORTED;      // one lane per coordinate component
     if (n_nodes == 0) return MDX_OK;
     if (!hidden || !w_out || !coord_diff || !offsets || !degree || !trans) return MDX_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(egnn_coord_head_kernel, dim3(node_grid(n_nodes)), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(egnn_coord_head_kernel, dim3(node_grid(n_nodes)), dim3(kBlock), 0, as_stream(stream),
                        hidden, w_out, coord_diff, offsets, degree, n_nodes, H, spatial_dimension, mean, trans);
-    return hipGetLastError() == hipSuccess ? MDX_OK : MDX_ERR_HIP;
+    return launch_status();
 }
 
 int mdx_segment_rows(const float* data, const int64_t* offsets, const int64_t* degree, int64_t n_nodes, int H, int mean,
@@ -463,9 +465,9 @@ int mdx_segment_rows(const float* data, const int64_t* offsets, const int64_t* d
     if (H & 3) return MDX_ERR_UNSUPPORTED;
     if (n_nodes == 0) return MDX_OK;
     if (!data || !offsets || !degree || !out) return MDX_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(segment_rows_kernel, dim3(node_grid(n_nodes)), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(segment_rows_kernel, dim3(node_grid(n_nodes)), dim3(kBlock), 0, as_stream(stream),
                        data, offsets, degree, n_nodes, H, mean, out);
-    return hipGetLastError() == hipSuccess ? MDX_OK : MDX_ERR_HIP;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -19,11 +19,13 @@
 #include <stdint.h>
 
 #include "../../include/mdx_hip.h"
+#include "mdx_launch.hpp"
+
+using namespace mdx;
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-constexpr int kWave = 64;
 
 // 4-point Lagrange weights on the nodes -1, 0, 1, 2 at t in [0, 1] (t = 1/2: -1/16, 9/16, 9/16, -1/16, all exact)
 __device__ __forceinline__ void lagrange_weights(float t, float w[4])
@@ -256,12 +258,12 @@ int mdx_egnn_table_check(const float* table, const float* table_scalar, int H, i
     if (H < 1 || n_classes < 1 || n_even < 4 || n_sigma < 1 || !(tolerance >= 0.0f)) return MDX_ERR_INVALID_ARG;
     if (!table || !table_scalar || !sigma || !workspace) return MDX_ERR_INVALID_ARG;
     const int n_pairs = n_classes * n_classes;
-    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const hipStream_t s = as_stream(stream);
     hipLaunchKernelGGL(egnn_table_check_kernel, dim3((unsigned)n_pairs, (unsigned)((n_even - 2 + kCheckRows - 1) / kCheckRows)),
                        dim3(256), 0, s, table, table_scalar, H, n_pairs, n_even, reinterpret_cast<unsigned*>(workspace));
     hipLaunchKernelGGL(egnn_table_verdict_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<unsigned*>(workspace), n_pairs,
                        H + 1, sigma, n_sigma, tolerance, worst_out, status);
-    return hipGetLastError() == hipSuccess ? MDX_OK : MDX_ERR_HIP;
+    return launch_status();
 }
 
 int mdx_egnn_table_gather(const float* table, const float* table_scalar, int H, int n_classes, int n_even, float inv_spacing,
@@ -280,10 +282,10 @@ int mdx_egnn_table_gather(const float* table, const float* table_scalar, int H, 
         return MDX_ERR_INVALID_ARG;
     int64_t blocks = (n_nodes * kWave + 255) / 256;
     if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(egnn_table_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(egnn_table_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream),
                        table, table_scalar, H, n_classes, n_even, inv_spacing, atom_types, offsets, degree, n_nodes, mean_messages,
                        out, left, coord, edges, coord_dimension, mean_coords, coord_flags, coord_out, status);
-    return hipGetLastError() == hipSuccess ? MDX_OK : MDX_ERR_HIP;
+    return launch_status();
 }
 
 }  // extern "C"

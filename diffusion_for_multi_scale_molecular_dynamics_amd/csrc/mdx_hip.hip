@@ -1,5 +1,6 @@
-// HIP kernels (gfx950 / CDNA4) + C ABI of the sampling hot path.  See include/mdx_hip.h for the contract and
-// DESIGN.md for data layout, roofline accounting and the arithmetic specification.
+// HIP kernels (gfx950 / CDNA4) + C ABI of the sampling hot path: the schedule, the per-step updates and the fused MLP family,
+// which run one per-structure update (pc_update_structure).  See include/mdx_hip.h for the contract and DESIGN.md for data
+// layout, roofline accounting and the arithmetic specification.  The periodic pair kernels are in mdx_pairs.hip.
 //
 // Kernel inventory
 //   schedule_kernel        S1  variance-exploding schedule tables (one-off, one workgroup)
@@ -10,11 +11,9 @@
 //   adaptive_stats_kernel      adaptive corrector: per-structure score / noise norms on pc_step_kernel's lane mapping,
 //   adaptive_totals_kernel     their binary64 batch sums (+ the step size) behind a launch boundary, fixed order, no atomics,
 //   adaptive_update_kernel     and the update with {eps, sqrt(2 eps), sigma} read from device words
+//   mlp_forward_kernel, mlp_pack_image_kernel, pc_noise_fill_kernel, mlp_pc_sample_kernel
+//                              fused MLP score network and the persistent sampler built on it (one wavefront = one structure)
 //   repaint_rows_kernel    R1  forward-noise + scatter of the constrained rows (F1 + F2 fused)
-//   radius_graph_kernel    N1  27-image radius graph, structure tile staged in LDS, one wavefront per source
-//                              row, ballot/scan ranked writes => edges come out sorted, no atomics
-//   force_field_kernel         the force-field wrapper's pseudo-force on N1's tile and pair test, no edge list:
-//                              per-lane sums + a fixed cross-lane reduction, optional fused add to the score
 //   rng_fill_kernel            Philox draws as arrays
 // 64-wide wavefronts are assumed throughout (gfx950).
 #include <hip/hip_runtime.h>
@@ -22,25 +21,14 @@
 
 #include <atomic>
 #include <cmath>
-#include <cstdlib>
 
 #include "../../include/mdx_hip.h"
+#include "mdx_launch.hpp"
 #include "mdx_math.hpp"
 
 using namespace mdx;
 
 namespace {
-
-constexpr int kBlock = 256;
-constexpr int kWave = 64;
-
-// the call index of a counter-based RNG request: the device word when the request names one (launches captured into a hipGraph)
-__device__ __forceinline__ uint32_t rng_call(const mdx_rng_t& r) { return r.call_dev ? *r.call_dev : r.call; }
-
-
-inline int launch_status() { return hipGetLastError() == hipSuccess ? MDX_OK : MDX_ERR_HIP; }
-inline hipStream_t as_stream(mdx_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ---------------------------------------------------------------------------------------------------------------
 // S1
@@ -2112,547 +2100,6 @@ __global__ __launch_bounds__(kBlock) void forward_step_kernel(ForwardStepArgs p)
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// N1: radius graph
-// ---------------------------------------------------------------------------------------------------------------
-constexpr int kRowsPerBlock = 16;
-
-__device__ __forceinline__ float crossing_distance(const float* cell)
-{
-    const float* a1 = cell; const float* a2 = cell + 3; const float* a3 = cell + 6;
-    const float c12x = a1[1] * a2[2] - a1[2] * a2[1], c12y = a1[2] * a2[0] - a1[0] * a2[2], c12z = a1[0] * a2[1] - a1[1] * a2[0];
-    const float c13x = a1[1] * a3[2] - a1[2] * a3[1], c13y = a1[2] * a3[0] - a1[0] * a3[2], c13z = a1[0] * a3[1] - a1[1] * a3[0];
-    const float c23x = a2[1] * a3[2] - a2[2] * a3[1], c23y = a2[2] * a3[0] - a2[0] * a3[2], c23z = a2[0] * a3[1] - a2[1] * a3[0];
-    const float vol = __builtin_fabsf((c12x * a3[0] + c12y * a3[1]) + c12z * a3[2]);
-    const float n12 = __builtin_sqrtf((c12x * c12x + c12y * c12y) + c12z * c12z);
-    const float n13 = __builtin_sqrtf((c13x * c13x + c13y * c13y) + c13z * c13z);
-    const float n23 = __builtin_sqrtf((c23x * c23x + c23y * c23y) + c23z * c23z);
-    float dmin = vol / n12;
-    const float d2 = vol / n13;
-    if (d2 < dmin) dmin = d2;
-    const float d3 = vol / n23;
-    if (d3 < dmin) dmin = d3;
-    return dmin;
-}
-
-// Bit l of the result: image l (itertools.product(-1, 0, 1) order) of atom j lies within the cutoff of atom i, 0 < d^2 <= rc^2
-// (neighbors.py:192-194 excludes coincident atoms as well as the atom itself).  `ortho`: the cell is diagonal with
-// rc <= L_min / 2.2, so only the nearest image can qualify and ONE is evaluated, with the expression of the sweep: same bits.
-__device__ __forceinline__ uint32_t images_within_cutoff(bool ortho, float pix, float piy, float piz, float pjx, float pjy, float pjz,
-                                                         float inv_lx, float inv_ly, float inv_lz, float lx, float ly, float lz,
-                                                         const float* lv, float rc2)
-{
-    uint32_t mask = 0;
-    if (ortho) {
-        const int nx = max(-1, min(1, (int)__builtin_rintf((pix - pjx) * inv_lx)));
-        const int ny = max(-1, min(1, (int)__builtin_rintf((piy - pjy) * inv_ly)));
-        const int nz = max(-1, min(1, (int)__builtin_rintf((piz - pjz) * inv_lz)));
-        // image vector of a diagonal cell: n_k * L_k, exact, identical to the fma chain that fills lv[]
-        const float sx = pjx + (float)nx * lx, sy = pjy + (float)ny * ly, sz = pjz + (float)nz * lz;
-        const float dx = pix - sx, dy = piy - sy, dz = piz - sz;
-        const float d2 = (dx * dx + dy * dy) + dz * dz;
-        if (0.0f < d2 && d2 <= rc2) mask = (1u << ((nx + 1) * 9 + (ny + 1) * 3 + (nz + 1)));
-    } else {
-        // not unrolled: a full unroll hoists the 81 image-vector components into registers (113 VGPRs, half the
-        // occupancy) for the benefit of the rare triclinic path
-#pragma nounroll
-        for (int l = 0; l < 27; ++l) {
-            const float sx = pjx + lv[3 * l], sy = pjy + lv[3 * l + 1], sz = pjz + lv[3 * l + 2];
-            const float dx = pix - sx, dy = piy - sy, dz = piz - sz;
-            const float d2 = (dx * dx + dy * dy) + dz * dz;
-            if (0.0f < d2 && d2 <= rc2) mask |= (1u << l);
-        }
-    }
-    return mask;
-}
-
-// images_within_cutoff(...) != 0 for a caller that does not need to know WHICH image: the image number stays a float (rint, then
-// clamped to -1 .. 1 by a median) instead of going through an integer -- the same n, the same n * L, pj + n * L, pi - (...) and d^2,
-// ten instructions fewer per pair.  (A NaN difference gives n = 0 there and an unspecified n here; d^2 is NaN either way: no hit.)
-__device__ __forceinline__ bool any_image_within_cutoff(bool ortho, float pix, float piy, float piz, float pjx, float pjy, float pjz,
-                                                        float inv_lx, float inv_ly, float inv_lz, float lx, float ly, float lz,
-                                                        const float* lv, float rc2)
-{
-    if (!ortho) return images_within_cutoff(false, pix, piy, piz, pjx, pjy, pjz, inv_lx, inv_ly, inv_lz, lx, ly, lz, lv, rc2) != 0;
-    const float nx = __builtin_amdgcn_fmed3f(__builtin_rintf((pix - pjx) * inv_lx), -1.0f, 1.0f);
-    const float ny = __builtin_amdgcn_fmed3f(__builtin_rintf((piy - pjy) * inv_ly), -1.0f, 1.0f);
-    const float nz = __builtin_amdgcn_fmed3f(__builtin_rintf((piz - pjz) * inv_lz), -1.0f, 1.0f);
-    const float sx = pjx + nx * lx, sy = pjy + ny * ly, sz = pjz + nz * lz;
-    const float dx = pix - sx, dy = piy - sy, dz = piz - sz;
-    const float d2 = (dx * dx + dy * dy) + dz * dz;
-    return 0.0f < d2 && d2 <= rc2;
-}
-
-// One workgroup = one (structure, chunk of kRowsPerBlock source rows).  The structure's positions and its 27
-// image vectors are staged in LDS once; each wavefront then owns source rows and sweeps the destinations 64 at
-// a time.  Lane ranks from ballot/scan make the writes dense and ordered by (src, dst, image).
-template <bool FILL>
-__global__ __launch_bounds__(kBlock) void radius_graph_kernel(const float* __restrict__ cart, const float* __restrict__ cell,
-                                                              float rc, int64_t B, int N, int unique, int chunks,
-                                                              int64_t* __restrict__ counts, const int64_t* __restrict__ offsets,
-                                                              int64_t* __restrict__ edges, int32_t* __restrict__ image_out,
-                                                              float* __restrict__ shifts_out, uint32_t* status,
-                                                              int64_t capacity, const float* __restrict__ lattice,
-                                                              int lattice_stride, float clip_min)
-{
-    extern __shared__ float lds[];
-    float* pos = lds;            // [N][3]
-    float* lv = lds + 3 * N;     // [27][3]
-    const int64_t b = blockIdx.x / chunks;
-    const int chunk = blockIdx.x % chunks;
-    const float* P = cart + b * N * 3;
-    // lattice != nullptr (the EGNN score network's graph, egnn_score_network.py:236-247): `cart` holds RELATIVE coordinates and
-    // the cell is diag(max(lattice[b, k], clip_min)); relative x diagonal cell is one product per component -- the bits
-    // torch.matmul(relative, diag_embed(lengths)) gives (its other terms are exact zeros)
-    float cl[9];
-    if (lattice) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) cl[k] = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float v = lattice[b * lattice_stride + k];
-            cl[4 * k] = v < clip_min ? clip_min : v;          // torch.clip(min=): a NaN stays a NaN
-        }
-        for (int i = threadIdx.x; i < 3 * N; i += blockDim.x) {
-            const int c = i % 3;
-            pos[i] = P[i] * (c == 0 ? cl[0] : c == 1 ? cl[4] : cl[8]);
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) cl[k] = cell[b * 9 + k];
-        for (int i = threadIdx.x; i < 3 * N; i += blockDim.x) pos[i] = P[i];
-    }
-    if (threadIdx.x < 81) {
-        const int l = threadIdx.x / 3, c = threadIdx.x % 3;
-        const float rel[3] = {(float)(l / 9 - 1), (float)((l / 3) % 3 - 1), (float)(l % 3 - 1)};
-        float acc = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) acc = __builtin_fmaf(rel[k], c == 0 ? cl[k * 3] : c == 1 ? cl[k * 3 + 1] : cl[k * 3 + 2], acc);
-        lv[threadIdx.x] = acc;
-    }
-    if (!FILL && chunk == 0 && threadIdx.x == 96 && status) {
-        if (!(crossing_distance(cl) > rc)) atomicOr(status, MDX_STATUS_CUTOFF_TOO_LARGE);
-    }
-    // Orthorhombic cell with rc <= L_min / 2.2 (always true on the EGNN path, which clips the cell to 2.2 rc):
-    // an image within rc has every component |delta_k| <= rc <= 0.4546 L_k, so it is THE nearest image and the
-    // other 26 cannot qualify.  One image is then evaluated -- with the same expression, hence the same bits.
-    const bool ortho = cl[1] == 0.0f && cl[2] == 0.0f && cl[3] == 0.0f && cl[5] == 0.0f && cl[6] == 0.0f &&
-                       cl[7] == 0.0f && cl[0] > 0.0f && cl[4] > 0.0f && cl[8] > 0.0f &&
-                       rc * 2.2f <= fminf(cl[0], fminf(cl[4], cl[8]));
-    const float inv_lx = ortho ? 1.0f / cl[0] : 0.0f, inv_ly = ortho ? 1.0f / cl[4] : 0.0f,
-                inv_lz = ortho ? 1.0f / cl[8] : 0.0f;
-    __syncthreads();
-    const float rc2 = rc * rc;
-    const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-    const int row_end = min(N, (chunk + 1) * kRowsPerBlock);
-    for (int i = chunk * kRowsPerBlock + wave; i < row_end; i += kBlock / kWave) {
-        const float pix = pos[3 * i], piy = pos[3 * i + 1], piz = pos[3 * i + 2];
-        const int64_t row = b * N + i;
-        const int64_t base = FILL ? offsets[row] : 0;
-        int64_t running = 0;
-        for (int j0 = 0; j0 < N; j0 += kWave) {
-            const int j = j0 + lane;
-            uint32_t mask = 0;
-            if (j < N)
-                mask = images_within_cutoff(ortho, pix, piy, piz, pos[3 * j], pos[3 * j + 1], pos[3 * j + 2], inv_lx, inv_ly,
-                                            inv_lz, cl[0], cl[4], cl[8], lv, rc2);
-            int cnt, rank, total;
-            if (unique) {
-                cnt = (mask != 0);
-                const unsigned long long hits = __ballot(cnt);
-                rank = __popcll(hits & ((1ull << lane) - 1ull));
-                total = __popcll(hits);
-            } else {
-                cnt = __popc(mask);
-                int incl = cnt;                      // inclusive prefix over the lanes
-#pragma unroll
-                for (int o = 1; o < kWave; o <<= 1) {
-                    const int v = __shfl_up(incl, o, kWave);
-                    if (lane >= o) incl += v;
-                }
-                total = __shfl(incl, kWave - 1, kWave);
-                rank = incl - cnt;
-            }
-            if (FILL && cnt) {
-                int64_t e = base + running + rank;
-                if (unique) {
-                    longlong2 pair;
-                    pair.x = row;
-                    pair.y = row - i + j;
-                    if (e < capacity) reinterpret_cast<longlong2*>(edges)[e] = pair;      // one 16-B store per edge
-                } else {
-                    uint32_t m = mask;
-                    while (m && e < capacity) {
-                        const int l = __ffs(m) - 1;
-                        m &= m - 1;
-                        longlong2 pair;
-                        pair.x = i;
-                        pair.y = j;
-                        reinterpret_cast<longlong2*>(edges)[e] = pair;
-                        image_out[e] = l;
-                        if (shifts_out) {
-                            shifts_out[3 * e] = lv[3 * l];
-                            shifts_out[3 * e + 1] = lv[3 * l + 1];
-                            shifts_out[3 * e + 2] = lv[3 * l + 2];
-                        }
-                        ++e;
-                    }
-                }
-            }
-            running += total;
-        }
-        if (!FILL && lane == 0) counts[row] = running;
-        // a caller-sized edge list that is too small: nothing is written beyond it, and the caller is told
-        if (FILL && lane == 0 && status && base + running > capacity) atomicOr(status, MDX_STATUS_GRAPH_CAPACITY);
-    }
-}
-
-// The force-field wrapper's pseudo-force (force_field_augmented_score_network.py:86-236) straight from the coordinates: the
-// staging, the image set and the hit predicate of radius_graph_kernel in its lattice mode (so the edges are the ones the full
-// radius graph lists), and the reference's arithmetic per hit (i, j, image l):
-//   disp = (p_j - p_i) + shift_l,  r = |disp|,  c = two_s (r - rc) / (r + 1e-8) disp
-// Each lane sums its own hits; a fixed xor-butterfly over the 64 lanes then gives the row's sum, so a row depends on nothing but
-// its structure.  F_rel = F_cart x (1 / L) (the reference's matmul with inverse(diag(L)): its off-diagonal terms are exact zeros)
-// is rounded before the optional add of score_in -- the bits of raw.X + forces.  No edge list, no atomics, no workspace.
-__global__ __launch_bounds__(kBlock) void force_field_kernel(const float* __restrict__ relative, const float* __restrict__ lattice,
-                                                             int lattice_stride, float clip_min, float rc, float two_s, int N,
-                                                             int chunks, const float* __restrict__ score_in,
-                                                             float* __restrict__ out, uint32_t* status)
-{
-    extern __shared__ float lds[];
-    float* pos = lds;            // [N][3]
-    float* lv = lds + 3 * N;     // [27][3]
-    const int64_t b = blockIdx.x / chunks;
-    const int chunk = blockIdx.x % chunks;
-    const float* P = relative + b * N * 3;
-    float cl[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) cl[k] = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float v = lattice[b * lattice_stride + k];
-        cl[4 * k] = v < clip_min ? clip_min : v;              // torch.clip(min=): a NaN stays a NaN
-    }
-    for (int i = threadIdx.x; i < 3 * N; i += blockDim.x) {
-        const int c = i % 3;
-        pos[i] = P[i] * (c == 0 ? cl[0] : c == 1 ? cl[4] : cl[8]);
-    }
-    if (threadIdx.x < 81) {
-        const int l = threadIdx.x / 3, c = threadIdx.x % 3;
-        const float rel[3] = {(float)(l / 9 - 1), (float)((l / 3) % 3 - 1), (float)(l % 3 - 1)};
-        float acc = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) acc = __builtin_fmaf(rel[k], c == 0 ? cl[k * 3] : c == 1 ? cl[k * 3 + 1] : cl[k * 3 + 2], acc);
-        lv[threadIdx.x] = acc;
-    }
-    if (chunk == 0 && threadIdx.x == 96 && status) {
-        if (!(crossing_distance(cl) > rc)) atomicOr(status, MDX_STATUS_CUTOFF_TOO_LARGE);
-    }
-    const bool ortho = cl[0] > 0.0f && cl[4] > 0.0f && cl[8] > 0.0f && rc * 2.2f <= fminf(cl[0], fminf(cl[4], cl[8]));
-    const float inv_lx = ortho ? 1.0f / cl[0] : 0.0f, inv_ly = ortho ? 1.0f / cl[4] : 0.0f,
-                inv_lz = ortho ? 1.0f / cl[8] : 0.0f;
-    // relative = cartesian x inverse(diag(L)): the reciprocal of the clipped length, then one product per component
-    const float rx = 1.0f / cl[0], ry = 1.0f / cl[4], rz = 1.0f / cl[8];
-    __syncthreads();
-    const float rc2 = rc * rc;
-    const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-    const int row_end = min(N, (chunk + 1) * kRowsPerBlock);
-    for (int i = chunk * kRowsPerBlock + wave; i < row_end; i += kBlock / kWave) {
-        const float pix = pos[3 * i], piy = pos[3 * i + 1], piz = pos[3 * i + 2];
-        float fx = 0.0f, fy = 0.0f, fz = 0.0f;
-        for (int j0 = 0; j0 < N; j0 += kWave) {
-            const int j = j0 + lane;
-            if (j >= N) continue;
-            const float pjx = pos[3 * j], pjy = pos[3 * j + 1], pjz = pos[3 * j + 2];
-            uint32_t m = images_within_cutoff(ortho, pix, piy, piz, pjx, pjy, pjz, inv_lx, inv_ly, inv_lz, cl[0], cl[4], cl[8],
-                                              lv, rc2);
-            while (m) {
-                const int l = __ffs(m) - 1;
-                m &= m - 1;
-                const float dx = (pjx - pix) + lv[3 * l], dy = (pjy - piy) + lv[3 * l + 1], dz = (pjz - piz) + lv[3 * l + 2];
-                const float r = __builtin_sqrtf((dx * dx + dy * dy) + dz * dz);
-                const float c = two_s * (r - rc) / (r + 1.0e-8f);
-                fx += c * dx;
-                fy += c * dy;
-                fz += c * dz;
-            }
-        }
-#pragma unroll
-        for (int o = kWave / 2; o > 0; o >>= 1) {
-            fx += __shfl_xor(fx, o, kWave);
-            fy += __shfl_xor(fy, o, kWave);
-            fz += __shfl_xor(fz, o, kWave);
-        }
-        if (lane == 0) {
-            const int64_t row = (b * N + i) * 3;
-            const float gx = fx * rx, gy = fy * ry, gz = fz * rz;
-            out[row] = score_in ? score_in[row] + gx : gx;
-            out[row + 1] = score_in ? score_in[row + 1] + gy : gy;
-            out[row + 2] = score_in ? score_in[row + 2] + gz : gz;
-        }
-    }
-}
-
-// offsets[i] = counts[0] + ... + counts[i-1], *total = the sum: ONE workgroup walks the list in tiles of 16 384 entries (the list is
-// the per-atom edge count of a batch -- 32 768 entries, two tiles, at C3; a launch of its own between the two radius-graph passes
-// costs less than the three library launches of cumsum + subtraction it replaces).  A tile is kScanRows rows of 2 x kScanBlock
-// entries; thread t owns entries 2t, 2t + 1 of every row, so each of its loads and stores is one coalesced 16-byte lane access
-// (a thread owning 16 CONSECUTIVE entries made every wavefront-wide access touch 64 cache lines: 18 us instead of 6).  The sums
-// inside a tile are 32-bit (an entry is the edge count of ONE atom: < 2^13 at the largest structure the radius graph takes,
-// 16 384 of them < 2^27), the carry between tiles 64-bit.
-constexpr int kScanBlock = 1024, kScanRows = 8, kScanWaves = kScanBlock / kWave;
-
-// inclusive prefix sum over the 64 lanes with DPP adds (no LDS): within rows of 16 lanes, then lane 15 of rows 0 / 2 into rows
-// 1 / 3, then lane 31 into the upper half
-__device__ __forceinline__ int wave_inclusive_scan(int x)
-{
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);      // row_shr:1
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false);      // row_shr:2
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false);      // row_shr:4
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false);      // row_shr:8
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);      // row_bcast:15 into rows 1 and 3
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);      // row_bcast:31 into rows 2 and 3
-    return x;
-}
-
-__global__ __launch_bounds__(kScanBlock) void offsets_scan_kernel(const int64_t* __restrict__ counts, int64_t n,
-                                                                  int64_t* __restrict__ offsets, int64_t* __restrict__ total)
-{
-    // per (row, wavefront) sums of a tile, then their exclusive prefix in row-major order; [parity of the tile] so that a
-    // wavefront one barrier ahead does not write what a slower one still reads
-    __shared__ int sums[2][kScanRows * kScanWaves + 1];
-    const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-    int64_t carry = 0;
-    int parity = 0;
-    for (int64_t base = 0; base < n; base += (int64_t)kScanRows * 2 * kScanBlock, parity ^= 1) {
-        int* tile_sums = sums[parity];
-        int v0[kScanRows], v1[kScanRows], incl[kScanRows];
-#pragma unroll
-        for (int r = 0; r < kScanRows; ++r) {
-            const int64_t i = base + ((int64_t)r * kScanBlock + threadIdx.x) * 2;
-            if (i + 1 < n) {
-                const longlong2 pair = *reinterpret_cast<const longlong2*>(counts + i);
-                v0[r] = (int)pair.x;
-                v1[r] = (int)pair.y;
-            } else {
-                v0[r] = i < n ? (int)counts[i] : 0;
-                v1[r] = 0;
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < kScanRows; ++r) {
-            incl[r] = wave_inclusive_scan(v0[r] + v1[r]);
-            if (lane == kWave - 1) tile_sums[r * kScanWaves + wave] = incl[r];
-        }
-        __syncthreads();
-        if (wave == 0) {
-            // 128 sums, two per lane, in row-major order -> what lies before each of them in the tile; the tile's total behind
-            static_assert(kScanRows * kScanWaves == 2 * kWave, "one wavefront scans the tile's sums two per lane");
-            const int a = tile_sums[2 * lane], b = tile_sums[2 * lane + 1];
-            const int through = wave_inclusive_scan(a + b);
-            tile_sums[2 * lane] = through - a - b;
-            tile_sums[2 * lane + 1] = through - b;
-            if (lane == kWave - 1) tile_sums[kScanRows * kScanWaves] = through;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < kScanRows; ++r) {
-            const int64_t i = base + ((int64_t)r * kScanBlock + threadIdx.x) * 2;
-            const int64_t first = carry + (tile_sums[r * kScanWaves + wave] + (incl[r] - v0[r] - v1[r]));
-            if (i + 1 < n) {
-                longlong2 pair;
-                pair.x = first;
-                pair.y = first + v0[r];
-                *reinterpret_cast<longlong2*>(offsets + i) = pair;
-            } else if (i < n) {
-                offsets[i] = first;
-            }
-        }
-        carry += tile_sums[kScanRows * kScanWaves];
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// N1 as the EGNN score network builds it, in TWO launches: hit masks, then emission
-// ---------------------------------------------------------------------------------------------------------------
-// count -> scan -> fill evaluates every pair twice and puts a one-workgroup scan of B*N counts between two chip-wide launches.  Here
-// the adjacency of a structure is kept as what the ballot already is -- one 64-bit word per (source row, 64 destinations) -- in a
-// caller's workspace (N = 64: 512 bytes per structure); the second launch needs no positions and no arithmetic: it sums the totals
-// of the structures before its own (B words), scans its N row counts, and turns the words into ordered 16-byte pairs.
-// One workgroup per structure in both; a wavefront owns a CONTIGUOUS run of source rows, so its edges are one contiguous run of the
-// list and the write position is a running sum.  Same pair test as radius_graph_kernel (images_within_cutoff): same edges, same order.
-constexpr int kGraphMaxAtoms = 1024, kGraphMaxBatch = 2048;
-
-template <int THREADS>
-__global__ __launch_bounds__(THREADS) void egnn_graph_mask_kernel(const float* __restrict__ relative, const float* __restrict__ lattice,
-                                                                   int lattice_stride, float clip_min, float rc, int N,
-                                                                   int64_t* __restrict__ counts, unsigned long long* __restrict__ masks,
-                                                                   int64_t* __restrict__ totals, uint32_t* status)
-{
-    extern __shared__ float lds[];
-    float* pos = lds;                                    // [N][3]
-    float* lv = lds + 3 * N;                             // [27][3]
-    int* wave_total = reinterpret_cast<int*>(lv + 81);   // [THREADS / kWave]
-    const int64_t b = blockIdx.x;
-    const float* P = relative + b * N * 3;
-    float cl[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) cl[k] = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float v = lattice[b * lattice_stride + k];
-        cl[4 * k] = v < clip_min ? clip_min : v;             // torch.clip(min=): a NaN stays a NaN
-    }
-    for (int i = threadIdx.x; i < 3 * N; i += THREADS) {
-        const int c = i % 3;
-        pos[i] = P[i] * (c == 0 ? cl[0] : c == 1 ? cl[4] : cl[8]);
-    }
-    if (threadIdx.x < 81) {
-        const int l = threadIdx.x / 3, c = threadIdx.x % 3;
-        const float rel[3] = {(float)(l / 9 - 1), (float)((l / 3) % 3 - 1), (float)(l % 3 - 1)};
-        float acc = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) acc = __builtin_fmaf(rel[k], c == 0 ? cl[k * 3] : c == 1 ? cl[k * 3 + 1] : cl[k * 3 + 2], acc);
-        lv[threadIdx.x] = acc;
-    }
-    if (threadIdx.x == 96 && status) {
-        if (!(crossing_distance(cl) > rc)) atomicOr(status, MDX_STATUS_CUTOFF_TOO_LARGE);
-    }
-    const bool ortho = cl[0] > 0.0f && cl[4] > 0.0f && cl[8] > 0.0f && rc * 2.2f <= fminf(cl[0], fminf(cl[4], cl[8]));
-    const float inv_lx = ortho ? 1.0f / cl[0] : 0.0f, inv_ly = ortho ? 1.0f / cl[4] : 0.0f, inv_lz = ortho ? 1.0f / cl[8] : 0.0f;
-    __syncthreads();
-    const float rc2 = rc * rc;
-    const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-    const int words = (N + kWave - 1) / kWave;                           // per source row
-    const int rows = (N + THREADS / kWave - 1) / (THREADS / kWave);      // per wavefront, contiguous
-    const int first = wave * rows, last = min(N, first + rows);
-    int total = 0;
-    if (N <= kWave) {
-        // one word per row: the lane's destination atom stays in registers over the wavefront's rows
-        const int j = lane < N ? lane : 0;
-        const float pjx = pos[3 * j], pjy = pos[3 * j + 1], pjz = pos[3 * j + 2];
-        for (int i = first; i < last; ++i) {
-            const bool hit = any_image_within_cutoff(ortho, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], pjx, pjy, pjz, inv_lx, inv_ly,
-                                                     inv_lz, cl[0], cl[4], cl[8], lv, rc2);
-            const unsigned long long hits = __ballot(lane < N && hit);
-            const int count = __popcll(hits);
-            if (lane == 0) {
-                masks[b * N + i] = hits;
-                counts[b * N + i] = count;
-            }
-            total += count;
-        }
-    } else
-    for (int i = first; i < last; ++i) {
-        const float pix = pos[3 * i], piy = pos[3 * i + 1], piz = pos[3 * i + 2];
-        unsigned long long* row_words = masks + (b * N + i) * words;
-        int count = 0;
-        for (int w = 0; w < words; ++w) {
-            const int j = w * kWave + lane;
-            bool hit = false;
-            if (j < N)
-                hit = any_image_within_cutoff(ortho, pix, piy, piz, pos[3 * j], pos[3 * j + 1], pos[3 * j + 2], inv_lx, inv_ly,
-                                              inv_lz, cl[0], cl[4], cl[8], lv, rc2);
-            const unsigned long long hits = __ballot(hit);
-            if (lane == 0) row_words[w] = hits;
-            count += __popcll(hits);
-        }
-        if (lane == 0) counts[b * N + i] = count;
-        total += count;
-    }
-    if (lane == 0) wave_total[wave] = total;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t sum = 0;
-        for (int w = 0; w < THREADS / kWave; ++w) sum += wave_total[w];
-        totals[b] = sum;
-    }
-}
-
-template <int THREADS>
-__global__ __launch_bounds__(THREADS) void egnn_graph_emit_kernel(int N, int64_t B, const int64_t* __restrict__ counts,
-                                                                   const unsigned long long* __restrict__ masks,
-                                                                   const int64_t* __restrict__ totals, int64_t* __restrict__ offsets,
-                                                                   int64_t* __restrict__ n_edges, int64_t* __restrict__ edges,
-                                                                   int64_t capacity, uint32_t* status)
-{
-    extern __shared__ int row_offset[];                  // [N + 1]: exclusive scan of the structure's row counts, the total behind
-    __shared__ int64_t partial[THREADS / kWave];
-    const int64_t b = blockIdx.x;
-    const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-    const int words = (N + kWave - 1) / kWave;
-    const int rows = (N + THREADS / kWave - 1) / (THREADS / kWave);
-    const int first = min(N, wave * rows), last = min(N, first + rows);
-    const int n_words = (last - first) * words;          // this wavefront's hit words: one contiguous run
-    const unsigned long long* my_words = masks + (b * N + first) * words;
-    unsigned long long held = lane < n_words ? my_words[lane] : 0ull;        // requested before anything waits
-    // edges of the structures before this one
-    int64_t before = 0;
-    for (int64_t k = threadIdx.x; k < b; k += THREADS) before += totals[k];
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) before += __shfl_xor(before, o, kWave);
-    if (lane == 0) partial[wave] = before;
-    if (wave == 0) {
-        int carry = 0;
-        for (int c0 = 0; c0 < N; c0 += kWave) {
-            const int i = c0 + lane;
-            const int v = i < N ? (int)counts[b * N + i] : 0;
-            const int incl = wave_inclusive_scan(v);
-            if (i < N) row_offset[i] = carry + incl - v;
-            carry += __shfl(incl, kWave - 1, kWave);
-        }
-        if (lane == 0) row_offset[N] = carry;
-    }
-    __syncthreads();
-    int64_t base = 0;
-#pragma unroll
-    for (int w = 0; w < THREADS / kWave; ++w) base += partial[w];
-    for (int i = threadIdx.x; i < N; i += THREADS) offsets[b * N + i] = base + row_offset[i];
-    const int total = row_offset[N];
-    if (threadIdx.x == 0) {
-        if (b == B - 1) *n_edges = base + total;
-        // a caller-sized edge list that is too small: nothing is written beyond it, and the caller is told
-        if (status && base + total > capacity) atomicOr(status, MDX_STATUS_GRAPH_CAPACITY);
-    }
-    if (n_words == 0) return;
-    int64_t e = base + row_offset[first];
-    int64_t src = b * N + first;
-    int w_in_row = 0;
-    for (int c0 = 0; c0 < n_words; c0 += kWave) {
-        if (c0) held = c0 + lane < n_words ? my_words[c0 + lane] : 0ull;
-        const int limit = min(kWave, n_words - c0);
-        for (int k = 0; k < limit; ++k) {
-            const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)held, k), hi = __builtin_amdgcn_readlane((uint32_t)(held >> 32), k);
-            const unsigned long long hits = ((unsigned long long)hi << 32) | lo;
-            if ((hits >> lane) & 1ull) {
-                const int64_t at = e + __popcll(hits & ((1ull << lane) - 1ull));
-                longlong2 pair;
-                pair.x = src;
-                pair.y = b * N + w_in_row * kWave + lane;
-                if (at < capacity) reinterpret_cast<longlong2*>(edges)[at] = pair;        // one 16-B store per edge
-            }
-            e += __popcll(hits);
-            if (++w_in_row == words) { w_in_row = 0; ++src; }
-        }
-    }
-}
-
-template <int THREADS>
-static void launch_graph_two_pass(const float* relative_coordinates, const float* lattice_parameters, int lattice_stride, float clip_min,
-                                  float rc, int64_t batch, int N, int64_t capacity, int64_t* counts, int64_t* offsets,
-                                  int64_t* n_edges, int64_t* edges_out, uint32_t* status, uint64_t* workspace, hipStream_t stream)
-{
-    unsigned long long* masks = reinterpret_cast<unsigned long long*>(workspace);
-    int64_t* totals = reinterpret_cast<int64_t*>(workspace) + batch * N * (int64_t)cdiv(N, kWave);
-    const size_t lds = sizeof(float) * (3 * (size_t)N + 81) + sizeof(int) * (THREADS / kWave);
-    hipLaunchKernelGGL(egnn_graph_mask_kernel<THREADS>, dim3((unsigned)batch), dim3(THREADS), lds, stream, relative_coordinates,
-                       lattice_parameters, lattice_stride, clip_min, rc, N, counts, masks, totals, status);
-    hipLaunchKernelGGL(egnn_graph_emit_kernel<THREADS>, dim3((unsigned)batch), dim3(THREADS), sizeof(int) * ((size_t)N + 1), stream,
-                       N, batch, (const int64_t*)counts, (const unsigned long long*)masks, (const int64_t*)totals, offsets, n_edges,
-                       edges_out, capacity, status);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
 // RNG fills and math probes
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void rng_fill_kernel(int kind, uint64_t seed, uint32_t call, uint32_t draw, uint32_t tag,
@@ -2694,16 +2141,6 @@ __global__ __launch_bounds__(kBlock) void math_probe_kernel(int fn, const float*
         y[i] = r;
     }
 }
-
-inline unsigned flat_grid(int64_t work_items)
-{
-    int64_t blocks = cdiv(work_items, kBlock);
-    if (blocks > 2048) blocks = 2048;   // 256 CUs x 8 resident blocks; the rest is grid-strided
-    if (blocks < 1) blocks = 1;
-    return (unsigned)blocks;
-}
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
 
@@ -3121,113 +2558,6 @@ int mdx_forward_diffusion_step(const mdx_schedule_t* sched_host, int index_i, co
     a.x = x_inout; a.a = a_inout;
     hipLaunchKernelGGL(forward_step_kernel, dim3(flat_grid(a.atoms)), dim3(kBlock), 0, as_stream(stream), a);
     return launch_status();
-}
-
-static int radius_graph_args_ok(const float* cart, const float* cell, float rc, int64_t batch, int N)
-{
-    if (batch < 0 || N < 1 || !(rc > 0.0f)) return MDX_ERR_INVALID_ARG;
-    if (N > 5000) return MDX_ERR_UNSUPPORTED;    // structure tile (12 B per atom) kept under the 64 KiB default dynamic-LDS limit
-    if (batch > 0 && (!cart || !cell)) return MDX_ERR_INVALID_ARG;
-    return MDX_OK;
-}
-
-int mdx_radius_graph_count(const float* cart, const float* cell, float rc, int64_t batch, int N, int unique,
-                           int64_t* counts, uint32_t* status, mdx_stream_t stream)
-{
-    const int ok = radius_graph_args_ok(cart, cell, rc, batch, N);
-    if (ok != MDX_OK) return ok;
-    if (batch == 0) return MDX_OK;
-    if (!counts) return MDX_ERR_INVALID_ARG;
-    const int chunks = (int)cdiv(N, kRowsPerBlock);
-    const size_t lds = sizeof(float) * (3 * (size_t)N + 81);
-    hipLaunchKernelGGL(radius_graph_kernel<false>, dim3((unsigned)(batch * chunks)), dim3(kBlock), lds, as_stream(stream),
-                       cart, cell, rc, batch, N, unique, chunks, counts, (const int64_t*)nullptr, (int64_t*)nullptr,
-                       (int32_t*)nullptr, (float*)nullptr, status, (int64_t)0, (const float*)nullptr, 0, 0.0f);
-    return launch_status();
-}
-
-int mdx_radius_graph_fill_capped(const float* cart, const float* cell, float rc, int64_t batch, int N, int unique,
-                                 const int64_t* offsets, int64_t capacity, int64_t* edges_out, int32_t* image_out,
-                                 float* shifts_out, uint32_t* status, mdx_stream_t stream)
-{
-    const int ok = radius_graph_args_ok(cart, cell, rc, batch, N);
-    if (ok != MDX_OK) return ok;
-    if (capacity < 0) return MDX_ERR_INVALID_ARG;
-    if (batch == 0) return MDX_OK;
-    if (!offsets || (capacity > 0 && !edges_out) || (!unique && capacity > 0 && !image_out)) return MDX_ERR_INVALID_ARG;
-    const int chunks = (int)cdiv(N, kRowsPerBlock);
-    const size_t lds = sizeof(float) * (3 * (size_t)N + 81);
-    hipLaunchKernelGGL(radius_graph_kernel<true>, dim3((unsigned)(batch * chunks)), dim3(kBlock), lds, as_stream(stream),
-                       cart, cell, rc, batch, N, unique, chunks, (int64_t*)nullptr, offsets, edges_out, image_out,
-                       shifts_out, status, capacity, (const float*)nullptr, 0, 0.0f);
-    return launch_status();
-}
-
-int64_t mdx_egnn_radius_graph_workspace_words(int64_t batch, int N)
-{
-    if (batch < 1 || N < 1 || N > kGraphMaxAtoms || batch > kGraphMaxBatch) return 0;
-    return batch * N * (int64_t)cdiv(N, kWave) + batch;
-}
-
-int mdx_egnn_radius_graph(const float* relative_coordinates, const float* lattice_parameters, int lattice_stride, float clip_min,
-                          float rc, int64_t batch, int N, int64_t capacity, int64_t* counts, int64_t* offsets,
-                          int64_t* n_edges, int64_t* edges_out, uint32_t* status, uint64_t* workspace, int64_t workspace_words,
-                          mdx_stream_t stream)
-{
-    if (batch < 0 || N < 1 || !(rc > 0.0f) || capacity < 0 || lattice_stride < 3 || !(clip_min >= 0.0f)) return MDX_ERR_INVALID_ARG;
-    if (N > 5000) return MDX_ERR_UNSUPPORTED;
-    if (!n_edges) return MDX_ERR_INVALID_ARG;
-    if (batch == 0) return hipMemsetAsync(n_edges, 0, sizeof(int64_t), as_stream(stream)) == hipSuccess ? MDX_OK : MDX_ERR_HIP;
-    if (!relative_coordinates || !lattice_parameters || !counts || !offsets || (capacity > 0 && !edges_out)) return MDX_ERR_INVALID_ARG;
-    if (workspace_words < 0 || (workspace_words > 0 && !workspace)) return MDX_ERR_INVALID_ARG;
-    const int64_t needed = mdx_egnn_radius_graph_workspace_words(batch, N);
-    if (workspace && needed > 0) {
-        if (workspace_words < needed) return MDX_ERR_INVALID_ARG;
-        // sixteen wavefronts per structure while the launch still fits the chip at once (8 192 wavefront slots), four beyond
-        if (N <= 16 || (N <= kWave && batch > 768))
-            launch_graph_two_pass<256>(relative_coordinates, lattice_parameters, lattice_stride, clip_min, rc, batch, N, capacity,
-                                       counts, offsets, n_edges, edges_out, status, workspace, as_stream(stream));
-        else
-            launch_graph_two_pass<1024>(relative_coordinates, lattice_parameters, lattice_stride, clip_min, rc, batch, N, capacity,
-                                        counts, offsets, n_edges, edges_out, status, workspace, as_stream(stream));
-        return launch_status();
-    }
-    const int chunks = (int)cdiv(N, kRowsPerBlock);
-    const size_t lds = sizeof(float) * (3 * (size_t)N + 81);
-    const dim3 grid((unsigned)(batch * chunks));
-    hipLaunchKernelGGL(radius_graph_kernel<false>, grid, dim3(kBlock), lds, as_stream(stream), relative_coordinates,
-                       (const float*)nullptr, rc, batch, N, 1, chunks, counts, (const int64_t*)nullptr, (int64_t*)nullptr,
-                       (int32_t*)nullptr, (float*)nullptr, status, (int64_t)0, lattice_parameters, lattice_stride, clip_min);
-    hipLaunchKernelGGL(offsets_scan_kernel, dim3(1), dim3(kScanBlock), 0, as_stream(stream), (const int64_t*)counts, batch * N,
-                       offsets, n_edges);
-    hipLaunchKernelGGL(radius_graph_kernel<true>, grid, dim3(kBlock), lds, as_stream(stream), relative_coordinates,
-                       (const float*)nullptr, rc, batch, N, 1, chunks, (int64_t*)nullptr, (const int64_t*)offsets, edges_out,
-                       (int32_t*)nullptr, (float*)nullptr, status, capacity, lattice_parameters, lattice_stride, clip_min);
-    return launch_status();
-}
-
-int mdx_force_field_pseudo_force(const float* relative_coordinates, const float* lattice_parameters, int lattice_stride,
-                                 float clip_min, float rc, float two_strength, int64_t batch, int N, const float* score_in,
-                                 float* out, uint32_t* status, mdx_stream_t stream)
-{
-    if (batch < 0 || N < 1 || !(rc > 0.0f) || lattice_stride < 3 || !(clip_min >= 0.0f)) return MDX_ERR_INVALID_ARG;
-    if (N > 5000) return MDX_ERR_UNSUPPORTED;    // the structure tile in LDS, as the radius graph's
-    if (batch == 0) return MDX_OK;
-    if (!relative_coordinates || !lattice_parameters || !out) return MDX_ERR_INVALID_ARG;
-    const int chunks = (int)cdiv(N, kRowsPerBlock);
-    const size_t lds = sizeof(float) * (3 * (size_t)N + 81);
-    hipLaunchKernelGGL(force_field_kernel, dim3((unsigned)(batch * chunks)), dim3(kBlock), lds, as_stream(stream),
-                       relative_coordinates, lattice_parameters, lattice_stride, clip_min, rc, two_strength, N, chunks, score_in,
-                       out, status);
-    return launch_status();
-}
-
-int mdx_radius_graph_fill(const float* cart, const float* cell, float rc, int64_t batch, int N, int unique,
-                          const int64_t* offsets, int64_t* edges_out, int32_t* image_out, float* shifts_out,
-                          mdx_stream_t stream)
-{
-    return mdx_radius_graph_fill_capped(cart, cell, rc, batch, N, unique, offsets, INT64_MAX, edges_out, image_out, shifts_out,
-                                        nullptr, stream);
 }
 
 static int mlp_ok(const mdx_mlp_t* m)

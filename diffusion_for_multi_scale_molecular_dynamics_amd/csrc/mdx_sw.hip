@@ -18,11 +18,12 @@
 #include <stdint.h>
 
 #include "../../include/mdx_hip.h"
+#include "mdx_launch.hpp"
+
+using namespace mdx;
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWave = 64;
 constexpr int kWaves = kBlock / kWave;
 constexpr int kMaxAtoms = 1024;
 constexpr int kMaxTypes = 8;
@@ -32,19 +33,9 @@ constexpr int kEps = 0, kSigma = 1, kA = 2, kLambda = 3, kGamma = 4, kCos0 = 5, 
 // reasons a structure ends with NaNs
 constexpr int kSmallSide = 1, kBadType = 2, kOverflow = 4, kNotFinite = 8;
 
-inline int launch_status() { return hipGetLastError() == hipSuccess ? MDX_OK : MDX_ERR_HIP; }
-inline hipStream_t as_stream(mdx_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-
 __device__ __forceinline__ const double* entry_of(const double* __restrict__ table, int n, int a, int b, int c)
 {
     return table + (size_t)((a * n + b) * n + c) * kEntry;
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
 }
 
 // One leg of a triplet: displacement from the centre, its length, exp(gamma sigma / (r - a sigma)) and
