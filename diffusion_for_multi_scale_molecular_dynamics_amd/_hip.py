@@ -36,7 +36,8 @@ ABI_SYMBOLS = (
     "mdx_mlp_pc_sample", "mdx_mlp_pc_sample_variant", "mdx_mlp_pc_sample_workspace_floats", "mdx_mlp_image_floats", "mdx_mlp_pack_image", "mdx_egnn_message_input", "mdx_egnn_coord_head", "mdx_segment_rows",
     "mdx_egnn_chain_image_bytes", "mdx_egnn_chain_pack", "mdx_egnn_chain_adapt_activation_exponents", "mdx_egnn_edge_chain", "mdx_egnn_piece_rows", "mdx_segment_combine", "mdx_egnn_node_gather", "mdx_mlp_chain_rows", "mdx_egnn_coord_aggregate",
     "mdx_egnn_node_inputs", "mdx_egnn_scores", "mdx_egnn_outputs", "mdx_node_mlp_rows", "mdx_node_mlp_rows_split",
-    "mdx_egnn_table_check", "mdx_egnn_table_gather", "mdx_rng_fill", "mdx_math_probe",
+    "mdx_egnn_table_check", "mdx_egnn_table_gather", "mdx_egnn_node_inputs_keyed", "mdx_egnn_edge_chain_keyed",
+    "mdx_egnn_table_check_keyed", "mdx_rng_fill", "mdx_math_probe",
     "mdx_stillinger_weber_workspace_doubles", "mdx_stillinger_weber_energy_forces",
 )
 MLP_MAX_HIDDEN = 8
@@ -230,6 +231,12 @@ def _declare(L):
     L.mdx_egnn_node_gather.argtypes = [vp, i64, vp, vp, i64, i32, i32, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp]
     L.mdx_egnn_table_check.restype = i32
     L.mdx_egnn_table_check.argtypes = [vp, vp, i32, i32, i32, vp, i64, f32, vp, vp, vp, vp]
+    L.mdx_egnn_node_inputs_keyed.restype = i32
+    L.mdx_egnn_node_inputs_keyed.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp]
+    L.mdx_egnn_edge_chain_keyed.restype = i32
+    L.mdx_egnn_edge_chain_keyed.argtypes = [C.POINTER(EgnnChain), vp, vp, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.mdx_egnn_table_check_keyed.restype = i32
+    L.mdx_egnn_table_check_keyed.argtypes = [vp, vp, i32, i32, i32, vp, i64, f32, vp, vp, vp, vp, vp]
     L.mdx_egnn_table_gather.restype = i32
     L.mdx_egnn_table_gather.argtypes = [vp, vp, i32, i32, i32, f32, vp, vp, vp, i64, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp]
     L.mdx_egnn_chain_adapt_activation_exponents.restype = i32

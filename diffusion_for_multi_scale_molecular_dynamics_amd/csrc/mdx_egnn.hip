@@ -75,8 +75,10 @@ __global__ __launch_bounds__(kBlock) void egnn_node_inputs_kernel(const float* _
                                                                   const float* __restrict__ w, const float* __restrict__ b,
                                                                   int F, int H, int64_t n_nodes, float* __restrict__ z,
                                                                   float* __restrict__ h, const float* __restrict__ w2,
-                                                                  const float* __restrict__ b2, int H2, float* __restrict__ h2)
+                                                                  const float* __restrict__ b2, int H2, float* __restrict__ h2,
+                                                                  const uint32_t* __restrict__ table_key)
 {
+    if (mdx::table_is_current(table_key, sigma)) return; // (the grid's class nodes of a table that is still valid)
     const int64_t stride = (int64_t)gridDim.x * blockDim.x, t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     // a second linear map of the same [sigma | one_hot] input (nullable): the first graph layer's per-node projections,
     // with w2 = P W, b2 = P b formed once on the host -- P (W x + b) without the [n_nodes, H] x [H, 2H] product
@@ -140,8 +142,10 @@ __global__ __launch_bounds__(kBlock) void egnn_node_inputs_rows_kernel(const flo
                                                                        int F, int H, int64_t n_nodes, float* __restrict__ z,
                                                                        float* __restrict__ h, const float* __restrict__ w2,
                                                                        const float* __restrict__ b2, int H2,
-                                                                       float* __restrict__ h2)
+                                                                       float* __restrict__ h2,
+                                                                       const uint32_t* __restrict__ table_key)
 {
+    if (mdx::table_is_current(table_key, sigma)) return; // (the grid's class nodes of a table that is still valid)
     extern __shared__ float tables[];                   // [ (1 + F) H | (1 + F) H2 ]
     float* t1 = tables;
     float* t2 = tables + (1 + F) * H;
@@ -391,6 +395,16 @@ int mdx_egnn_node_inputs(const float* x, const float* k_vectors, int n_k, const 
                          int64_t n_nodes, float* z_out, float* h_out, const float* second_weight, const float* second_bias,
                          int second_width, float* second_out, mdx_stream_t stream)
 {
+    return mdx_egnn_node_inputs_keyed(x, k_vectors, n_k, sigma, atoms_per_structure, atom_types, emb_weight, emb_bias, n_features,
+                                      H, n_nodes, z_out, h_out, second_weight, second_bias, second_width, second_out, nullptr,
+                                      stream);
+}
+
+int mdx_egnn_node_inputs_keyed(const float* x, const float* k_vectors, int n_k, const float* sigma, int atoms_per_structure,
+                               const int64_t* atom_types, const float* emb_weight, const float* emb_bias, int n_features, int H,
+                               int64_t n_nodes, float* z_out, float* h_out, const float* second_weight, const float* second_bias,
+                               int second_width, float* second_out, const uint32_t* table_key, mdx_stream_t stream)
+{
     if (n_nodes < 0 || n_k < 1 || atoms_per_structure < 1 || n_features < 2 || H < 1) return MDX_ERR_INVALID_ARG;
     if (n_nodes == 0) return MDX_OK;
     if (!x || !k_vectors || !sigma || !atom_types || !emb_weight || !emb_bias || !z_out || !h_out) return MDX_ERR_INVALID_ARG;
@@ -404,14 +418,14 @@ int mdx_egnn_node_inputs(const float* x, const float* k_vectors, int n_k, const 
         hipLaunchKernelGGL(egnn_node_inputs_rows_kernel, dim3((unsigned)blocks), dim3(kBlock), table_bytes,
                            as_stream(stream), x, k_vectors, n_k, sigma, atoms_per_structure, atom_types,
                            emb_weight, emb_bias, n_features, H, n_nodes, z_out, h_out, second_weight, second_bias, second_width,
-                           second_out);
+                           second_out, table_key);
         return launch_status();
     }
     int64_t blocks = (n_nodes * H + kBlock - 1) / kBlock;
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(egnn_node_inputs_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), x,
                        k_vectors, n_k, sigma, atoms_per_structure, atom_types, emb_weight, emb_bias, n_features, H, n_nodes,
-                       z_out, h_out, second_weight, second_bias, second_width, second_out);
+                       z_out, h_out, second_weight, second_bias, second_width, second_out, table_key);
     return launch_status();
 }
 

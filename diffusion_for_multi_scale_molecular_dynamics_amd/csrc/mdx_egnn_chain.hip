@@ -95,6 +95,10 @@ struct ChainArgs {
     float* proj_out;            // MODE 3, nullable: [M][2H] = out W_p^T for the 2 H x H layers that follow the MLP in the image
     float* rows_out;            // [M][H]
     void* stamp_buf;            // -DMDX_CHAIN_STAMPS builds only (else null): see MDX_STAMP_WRITE
+    // MODE 0 on the first layer's distance grid (mdx_egnn_edge_chain_keyed), else null: the key record of the table this launch
+    // would rebuild and the forward's sigma.  (Behind every other member: no other argument's offset moves.)
+    const uint32_t* table_key;
+    const float* table_sigma;
 };
 
 constexpr float kLog2e = 1.44269504088896340736f, kLn2 = 0.69314718055994530942f;
@@ -678,6 +682,15 @@ __global__ __launch_bounds__(kWaves* kWave, 1) void egnn_edge_chain_kernel(Chain
 {
     static_assert(!ATT || MODE == 0 || MODE == 2, "the attention gate belongs to the edge chain");
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+    // The table this launch would build is still the one in memory (its key holds the bits of this forward's sigma; a NaN never
+    // matches): nothing to do.  Two scalar loads and a compare, uniform over the launch; only the instantiation that runs on the
+    // grid has the test.
+    if constexpr (MODE == 0 && !ATT) {
+        if (p.table_key) {
+            const uint32_t key = p.table_key[0], bits = __float_as_uint(p.table_sigma[0]);
+            if (key == bits && (bits & 0x7fffffffu) <= 0x7f800000u) return;
+        }
+    }
     // (GUARD: see issue_piece.  The production-size piece-sums instantiations <256, PREC, 2> skip the three extra wait states
     // in front of their requests -- 2.2 % of the launch, A/B in profiles/r03_chain_ablation.md -- which is safe only while they
     // restore no scalar register from a vector register: the BUILD checks that (csrc/Makefile feeds the compiler's resource
@@ -1689,10 +1702,11 @@ __global__ __launch_bounds__(256) void egnn_node_gather_kernel(const float* __re
                     if (k < D) part[k] += (ci[k] - coord[dst * D + k]) * se;
             }
         }
-        // messages
+        // messages (pieces == null, uniform per launch: the caller reads the coordinates alone -- the last graph layer of a
+        // forward whose atom-type logits nobody reads)
         const float count = (mean_messages && deg > 0) ? (float)deg : 1.0f;      // (a true division: egnn_utils.py:66-68)
         const int64_t last_row = ((e1 - 1) & 15) == 15 ? ((e1 - 1) >> 4) : boundary_rows + node;
-        for (int q = lane; q < quads; q += kWave) {
+        for (int q = lane; pieces && q < quads; q += kWave) {
             f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
             for (int64_t e = e0 | 15; e < e1 - 1; e += 16) acc += reinterpret_cast<const f32x4*>(pieces + (e >> 4) * H)[q];
             if (deg > 0) acc += reinterpret_cast<const f32x4*>(pieces + last_row * H)[q];
@@ -1825,7 +1839,18 @@ int mdx_egnn_edge_chain(const mdx_egnn_chain_t* c, const float* node_proj, const
                         const int64_t* edges, int64_t n_edges, const int64_t* n_edges_dev, float* messages_out,
                         float* edge_scalar_out, uint32_t* status, mdx_stream_t stream)
 {
+    return mdx_egnn_edge_chain_keyed(c, node_proj, coord, coord_dimension, edges, n_edges, n_edges_dev, messages_out,
+                                     edge_scalar_out, status, nullptr, nullptr, stream);
+}
+
+int mdx_egnn_edge_chain_keyed(const mdx_egnn_chain_t* c, const float* node_proj, const float* coord, int coord_dimension,
+                              const int64_t* edges, int64_t n_edges, const int64_t* n_edges_dev, float* messages_out,
+                              float* edge_scalar_out, uint32_t* status, const uint32_t* table_key, const float* sigma,
+                              mdx_stream_t stream)
+{
     if (!c || n_edges < 0 || coord_dimension < 1) return MDX_ERR_INVALID_ARG;
+    // (the early return exists in the instantiation the grid runs: messages as rows, no gate)
+    if (table_key && (!sigma || c->message_mode != MDX_EGNN_MESSAGES_ROWS || c->attention_weight)) return MDX_ERR_INVALID_ARG;
     if (c->n_message_layers < 1 || c->n_coord_layers < 1 || (c->precision < 0 || c->precision > 2) ||
         (c->message_mode != MDX_EGNN_MESSAGES_ROWS && c->message_mode != MDX_EGNN_MESSAGES_PIECE_SUMS))
         return MDX_ERR_INVALID_ARG;
@@ -1845,6 +1870,7 @@ int mdx_egnn_edge_chain(const mdx_egnn_chain_t* c, const float* node_proj, const
     a.piece_sums = c->message_mode == MDX_EGNN_MESSAGES_PIECE_SUMS;
     if ((c->attention_weight == nullptr) != (c->attention_bias == nullptr)) return MDX_ERR_INVALID_ARG;
     a.att_w = c->attention_weight; a.att_b = c->attention_bias;
+    a.table_key = table_key; a.table_sigma = table_key ? sigma : nullptr;
 #ifdef MDX_CHAIN_STAMPS
     // (diagnostic builds: `status` is the caller's stamp list, uint64 [4096]; its entry count restarts with every launch)
     if (status && hipMemsetAsync((char*)status + 4095 * 8, 0, 8, reinterpret_cast<hipStream_t>(stream)) != hipSuccess) return MDX_ERR_HIP;
@@ -1908,7 +1934,9 @@ int mdx_egnn_node_gather(const float* pieces, int64_t n_edges, const int64_t* of
     if (coord_flags & ~(MDX_EGNN_COORD_NORMALIZE | MDX_EGNN_COORD_TANH)) return MDX_ERR_INVALID_ARG;
     if ((H & 3) || coord_dimension > 8) return MDX_ERR_UNSUPPORTED;
     if (n_nodes == 0) return MDX_OK;
-    if (!pieces || !offsets || !degree || !out || !edge_scalar || !coord || !edges || !coord_out) return MDX_ERR_INVALID_ARG;
+    if (!offsets || !degree || !edge_scalar || !coord || !edges || !coord_out) return MDX_ERR_INVALID_ARG;
+    // pieces == out == left == null: the coordinate half alone (the same bits as with the message half)
+    if (pieces ? !out : (out || left)) return MDX_ERR_INVALID_ARG;
     int64_t blocks = (n_nodes * kWave + 255) / 256;
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(egnn_node_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),

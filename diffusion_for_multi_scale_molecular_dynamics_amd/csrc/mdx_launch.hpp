@@ -30,6 +30,15 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
+// the key record of a memoised first-layer table (include/mdx_hip.h, mdx_egnn_table_check_keyed): was the table in memory
+// built at this sigma?  (nullable key: no record, never current; a NaN sigma is never current)
+__device__ __forceinline__ bool table_is_current(const uint32_t* key, const float* sigma)
+{
+    if (!key) return false;
+    const uint32_t bits = __float_as_uint(sigma[0]);
+    return key[0] == bits && (bits & 0x7fffffffu) <= 0x7f800000u;
+}
+
 inline int launch_status() { return hipGetLastError() == hipSuccess ? MDX_OK : MDX_ERR_HIP; }
 inline hipStream_t as_stream(mdx_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }

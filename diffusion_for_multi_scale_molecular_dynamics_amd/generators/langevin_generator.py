@@ -19,6 +19,7 @@ Same class name, constructor, step methods and behaviour as the reference's Lang
 
 There is no CPU fallback: calling this generator with device="cpu" raises.
 """
+import contextlib
 import dataclasses
 import gc
 import warnings
@@ -318,16 +319,25 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
     # one step = network forward + ONE fused update kernel
     # ---------------------------------------------------------------------------------------------------------
     def _step(self, mode: int, composition: AXL, index_i: int, cartesian_forces: torch.Tensor, draw_offset: int,
-              d_index: Optional[torch.Tensor] = None, in_place: bool = False):
+              d_index: Optional[torch.Tensor] = None, in_place: bool = False, predictions_unread: bool = False):
+        """predictions_unread: the caller drops the returned predictions (the device-resident loop)."""
         x = composition.X
         device = x.device
         sched = self._prepare(device)
         batch = x.shape[0]
         time_t, sigma_t = self._time_sigma(batch, device)
         kernels.fill_time_sigma(sched, mode, index_i, d_index, time_t, sigma_t)
-        predictions = self._get_model_predictions(composition, time_t, sigma_t, cartesian_forces)
-
         update_types = mode == MDX_PREDICTOR or self.atom_type_transition_in_corrector
+        # Nobody reads predictions.A of this step: the update does not touch the types, the caller drops the predictions, nothing
+        # is recorded, _get_model_predictions is LangevinGenerator's own (not a subclass's override, not a replacement set on the
+        # class or on the instance: whoever puts one there sees every forward whole) and no forward hook sits on the network or
+        # on a module inside it.  When in doubt the hint is not given.
+        unread = (predictions_unread and not update_types and not self.record and not self.record_atom_type_update
+                  and "_get_model_predictions" not in self.__dict__
+                  and type(self)._get_model_predictions is _OWN_GET_MODEL_PREDICTIONS and not hooks.outputs_watched(self.axl_network))
+        with hooks.logits_unread(self.axl_network) if unread else contextlib.nullcontext():
+            predictions = self._get_model_predictions(composition, time_t, sigma_t, cartesian_forces)
+
         z = gumbel = u = z_lattice = None
         if not self._device_rng:
             if mode == MDX_PREDICTOR:                                  # langevin_generator.py:280,416,623,633
@@ -568,7 +578,8 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
             comp, _ = self._step(MDX_PREDICTOR, comp, 1, forces, 0, d_index=d_index, in_place=True)
             comp = self._after_predictor(comp, 0, d_index=d_index)
             for m in range(self.number_of_corrector_steps):
-                comp, _ = self._step(MDX_CORRECTOR, comp, 0, forces, 1 + m, d_index=d_index, in_place=True)
+                comp, _ = self._step(MDX_CORRECTOR, comp, 0, forces, 1 + m, d_index=d_index, in_place=True,
+                                     predictions_unread=True)
             if self._visit < visits - 1:
                 comp = self._forward_step(comp, 0, d_index=d_index)
         self._visit = 0
@@ -656,6 +667,9 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
         if self.rng_mode == "device":
             self.noise_source = None
         return composition
+
+
+_OWN_GET_MODEL_PREDICTIONS = LangevinGenerator._get_model_predictions      # (as defined above: a later patch of the class differs)
 
 
 class IterationLoop:

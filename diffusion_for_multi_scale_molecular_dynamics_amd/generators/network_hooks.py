@@ -11,6 +11,8 @@ looked up on the live network at every use, never cached, so a network swapped o
   first_layer_table         set by the caller, and by table_off after a table report; read by reports_watched and capture_key.
                             Absent ("off"): no distance table, so no table report.
   sigma_uniform_hint        set by uniform_sigma around a forward, read by the network's forward.  Absent: a plain call.
+  logits_unread_hint        set by logits_unread around a forward whose atom-type logits nobody will read; the network may then
+                            return A = None and leave out the work behind the logits.  Absent: a plain call.
   capture_safe(B, N, dev)   the network's answer, asked by capture_safe.  Absent (True): the caller's use_hip_graph is believed.
   begin_f16_range_fallback  called by exact_f32 on entry.  Absent: no-op.
   adapt_f16_range           called by exact_f32 on exit.  Absent: no-op.
@@ -77,6 +79,30 @@ def uniform_sigma(net):
         yield
     finally:
         net.sigma_uniform_hint = False
+
+
+def outputs_watched(net) -> bool:
+    """Does a forward hook -- on the network, on a module inside it, or torch's global ones -- see outputs of the forward?  Then
+    the forward is run whole (no logits_unread)."""
+    import torch.nn.modules.module as m
+    if m._global_forward_hooks:
+        return True
+    modules = net.modules() if hasattr(net, "modules") else ()
+    return any(getattr(mod, "_forward_hooks", None) for mod in modules)
+
+
+@contextlib.contextmanager
+def logits_unread(net):
+    """Around a forward whose atom-type logits nobody reads (a corrector step that does not update the types, with nothing
+    recording or inspecting the predictions): the network may return A = None."""
+    if not hasattr(net, "logits_unread_hint"):
+        yield
+        return
+    net.logits_unread_hint = True
+    try:
+        yield
+    finally:
+        net.logits_unread_hint = False
 
 
 @contextlib.contextmanager

@@ -1014,15 +1014,27 @@ def mlp_chain_rows(pack: RowChainPack, x, residual=None, status=None) -> torch.T
     return out
 
 
-def egnn_edge_chain(pack: EdgeChainPack, node_proj, coord, edges, status=None, n_edges_dev=None, piece_sums: bool = False):
+def egnn_edge_chain(pack: EdgeChainPack, node_proj, coord, edges, status=None, n_edges_dev=None, piece_sums: bool = False,
+                    memo: Optional["EgnnTableMemo"] = None, sigma=None):
     """messages [E,H], edge_scalar [E] of the fused per-edge chain (mdx_egnn_edge_chain); edges sorted by source.
     n_edges_dev (int64 [1], device): the actual number of edge rows when `edges` is a capacity-sized list.
     piece_sums: the first output holds per-node piece sums instead of the messages, in the compact layout of
     mdx_egnn_piece_rows(E, n_nodes) = ceil(E / 16) + n_nodes rows (feed it to segment_combine with n_edges=E): no [E, H]
-    buffer exists in that mode."""
+    buffer exists in that mode.
+    memo (with sigma): the launch on the first layer's distance grid (mdx_egnn_edge_chain_keyed) -- the outputs are the memo's
+    kept buffers, and the kernel returns at once while the memo's key holds the bits of sigma[0]."""
     E, H = edges.shape[0], pack.hidden
     pack.c_struct.message_mode = 1 if piece_sums else 0
     assert node_proj.shape[1] == 2 * H and coord.shape[0] == node_proj.shape[0]
+    if memo is not None:
+        assert not piece_sums and sigma is not None and tuple(memo.values.shape) == (E, H)
+        rc = lib().mdx_egnn_edge_chain_keyed(C.byref(pack.c_struct), ptr(node_proj, F32, "node_proj"), ptr(coord, F32, "coord"),
+                                             coord.shape[1], ptr(edges, I64, "edges"), E, ptr(n_edges_dev, I64, "n_edges_dev"),
+                                             ptr(memo.values, F32, "messages"), ptr(memo.scalars, F32, "edge_scalar"),
+                                             ptr(status, I32, "status"), ptr(memo.key, I32, "table_key"),
+                                             ptr(sigma, F32, "sigma"), stream_handle())
+        check(rc, "mdx_egnn_edge_chain_keyed")
+        return memo.values, memo.scalars
     rows = lib().mdx_egnn_piece_rows(E, node_proj.shape[0]) if piece_sums else E
     messages = torch.empty(rows, H, dtype=F32, device=edges.device)
     scalar = torch.empty(E, dtype=F32, device=edges.device)
@@ -1056,7 +1068,17 @@ def coord_flags(normalize: bool, tanh: bool) -> int:
 def egnn_node_gather(pieces, n_edges: int, offsets, degree, mean_messages: bool, left, edge_scalar, coord, edges,
                      mean_coords: bool, flags: int = 0):
     """segment_combine(..., left=left) and egnn_coord_aggregate(...) in one launch (mdx_egnn_node_gather):
-    ([left | message sums] [n_nodes, 2H] (or the sums [n_nodes, H] when left is None), coord_out [n_nodes, D])."""
+    ([left | message sums] [n_nodes, 2H] (or the sums [n_nodes, H] when left is None), coord_out [n_nodes, D]).
+    pieces None (left None too): the coordinate half alone, (None, coord_out) with the same bits."""
+    if pieces is None:
+        assert left is None
+        coord_out = torch.empty_like(coord)
+        rc = lib().mdx_egnn_node_gather(None, n_edges, ptr(offsets, I64, "offsets"), ptr(degree, I64, "degree"), degree.shape[0],
+                                        4, int(bool(mean_messages)), None, None, ptr(edge_scalar, F32, "edge_scalar"),
+                                        ptr(coord, F32, "coord"), coord.shape[1], ptr(edges, I64, "edges"),
+                                        int(bool(mean_coords)), int(flags), ptr(coord_out, F32, "coord_out"), stream_handle())
+        check(rc, "mdx_egnn_node_gather")
+        return None, coord_out
     n_nodes, H = degree.shape[0], pieces.shape[1]
     assert left is None or tuple(left.shape) == (n_nodes, H)
     assert pieces.shape[0] == lib().mdx_egnn_piece_rows(n_edges, n_nodes), "pieces: not the compact layout of n_edges, n_nodes"
@@ -1079,16 +1101,53 @@ TABLE_INV_SPACING = 256.0        # h = 2^-8 between the even grid points: rho_k 
 TABLE_TOLERANCE = 2.0 ** -16
 
 
+TABLE_NO_KEY = 0x7fc00000        # MDX_EGNN_TABLE_NO_KEY: a NaN's bits in the key record = no table in memory
+
+
+class EgnnTableMemo:
+    """The first layer's distance table kept on the device between forwards (include/mdx_hip.h, "The table memoised on the
+    device"): the table's values [n_classes^2 K, H] and scalars, the grid problem's per-node inputs (of which the chain reads
+    `grid_proj` [G, 2H]), the check's workspace, and the KEY RECORD `key`, int32 [2] = (bits of the sigma the table was built
+    at, or TABLE_NO_KEY; number of builds so far).  The kernels of a build compare key[0] with the forward's sigma[0] on the
+    device and return at once when they agree; the verdict kernel writes the key.  One memo per first graph layer, device and
+    precision (E_GCL.table_memo): the pointers of a captured iteration stay valid across a one-iteration switch of precision.
+    `stamp`: whatever else the table depends on, kept by the owner, which calls reset() when it changes."""
+
+    def __init__(self, n_classes: int, n_even: int, hidden: int, embedding_width: int, coord_dimension: int, device):
+        K = 2 * n_even - 1
+        rows, G = n_classes * n_classes * K, n_classes * (K + 1)
+        self.n_classes, self.n_even = n_classes, n_even
+        self.values = torch.zeros(rows, hidden, dtype=F32, device=device)
+        self.scalars = torch.zeros(rows, dtype=F32, device=device)
+        self.grid_z = torch.zeros(G, coord_dimension, dtype=F32, device=device)
+        self.grid_h = torch.zeros(G, embedding_width, dtype=F32, device=device)
+        self.grid_proj = torch.zeros(G, 2 * hidden, dtype=F32, device=device)
+        self.workspace = torch.zeros(n_classes ** 2 * (hidden + 2), dtype=I32, device=device)      # (every check leaves it zeroed)
+        self.worst = torch.zeros(1, dtype=F32, device=device)
+        self.key = torch.tensor([TABLE_NO_KEY, 0], dtype=I32, device=device)
+        self.stamp = None
+
+    def reset(self):
+        """No table in memory: the next forward builds one.  A fill on the stream (no host read; the build counter stays)."""
+        self.key[:1].fill_(TABLE_NO_KEY)
+
+    def builds(self) -> int:
+        """The number of tables built so far (one host read: tests and evidence, not the hot path)."""
+        return int(self.key[1].item())
+
+
 @dataclass
 class EgnnTable:
     """What the first graph layer needs to run on the grid: the grid problem's per-node projections [G, 2H] (the class
     embeddings at the batch's sigma through the layer's first weight), sigma [B] (checked to be uniform on the device), the
-    nodes' classes [n_nodes] int64 (MASK = n_classes - 1) and the grid's size."""
+    nodes' classes [n_nodes] int64 (MASK = n_classes - 1) and the grid's size.  memo: the EgnnTableMemo that owns grid_proj and
+    receives the table."""
     grid_proj: torch.Tensor
     sigma: torch.Tensor
     atom_types: torch.Tensor
     n_classes: int
     n_even: int
+    memo: EgnnTableMemo
 
 
 def egnn_table_points(coord_dimension: int) -> int:
@@ -1121,14 +1180,17 @@ def egnn_table_grid(n_classes: int, n_even: int, coord_dimension: int, device):
     return _TABLE_GRIDS[key]
 
 
-def egnn_table_check(table, table_scalar, n_classes: int, n_even: int, sigma, workspace, worst=None, status=None):
-    """Midpoint check of the grid table (mdx_egnn_table_check): MDX_STATUS_EGNN_TABLE into `status` on failure."""
+def egnn_table_check(table, table_scalar, n_classes: int, n_even: int, sigma, workspace, worst=None, status=None, key=None):
+    """Midpoint check of the grid table (mdx_egnn_table_check): MDX_STATUS_EGNN_TABLE into `status` on failure.
+    key (EgnnTableMemo.key): mdx_egnn_table_check_keyed -- the midpoints only when this forward built the table, the uniform-sigma
+    check always, and the key record written last."""
     H = table.shape[1]
     assert table.shape[0] == n_classes * n_classes * (2 * n_even - 1) and workspace.numel() >= n_classes ** 2 * (H + 2)
-    rc = lib().mdx_egnn_table_check(ptr(table, F32, "table"), ptr(table_scalar, F32, "table_scalar"), H, n_classes, n_even,
-                                    ptr(sigma, F32, "sigma"), sigma.numel(), TABLE_TOLERANCE, ptr(workspace, I32, "workspace"),
-                                    ptr(worst, F32, "worst"), ptr(status, I32, "status"), stream_handle())
-    check(rc, "mdx_egnn_table_check")
+    rc = lib().mdx_egnn_table_check_keyed(ptr(table, F32, "table"), ptr(table_scalar, F32, "table_scalar"), H, n_classes, n_even,
+                                          ptr(sigma, F32, "sigma"), sigma.numel(), TABLE_TOLERANCE,
+                                          ptr(workspace, I32, "workspace"), ptr(worst, F32, "worst"), ptr(status, I32, "status"),
+                                          ptr(key, I32, "table_key"), stream_handle())
+    check(rc, "mdx_egnn_table_check_keyed")
 
 
 def egnn_table_gather(table, table_scalar, n_classes: int, n_even: int, atom_types, offsets, degree, mean_messages: bool, left,
@@ -1149,25 +1211,33 @@ def egnn_table_gather(table, table_scalar, n_classes: int, n_even: int, atom_typ
     return out, coord_out
 
 
-def egnn_node_inputs(x, k_vectors, sigma, atom_types, emb_weight, emb_bias, second=None):
+def egnn_node_inputs(x, k_vectors, sigma, atom_types, emb_weight, emb_bias, second=None, memo: Optional[EgnnTableMemo] = None):
     """z [n_nodes, 2 n_k] (torus uplift) and h [n_nodes, H] (embedding of [sigma | one_hot]) of EGNNScoreNetwork, one launch.
     x [B, N, 3] relative coordinates, sigma [B] (or [B,1]), atom_types [B, N] int64.
-    second = (W2 [H2, F], b2 [H2]): a third output, the same input through that linear map (see mdx_egnn_node_inputs)."""
+    second = (W2 [H2, F], b2 [H2]): a third output, the same input through that linear map (see mdx_egnn_node_inputs).
+    memo: the launch on the class nodes of the first layer's distance grid (mdx_egnn_node_inputs_keyed) -- the outputs are the
+    memo's kept buffers, and the kernel returns at once while the memo's key holds the bits of sigma[0]."""
     B, N, d = x.shape
     assert d == 3 and k_vectors.shape[1] == 3
     n_nodes, n_k, (H, F) = B * N, k_vectors.shape[0], emb_weight.shape
-    z = torch.empty(n_nodes, 2 * n_k, dtype=F32, device=x.device)
-    h = torch.empty(n_nodes, H, dtype=F32, device=x.device)
     w2, b2 = second if second is not None else (None, None)
     assert second is None or (w2.shape[1] == F and b2.shape[0] == w2.shape[0])
     H2 = w2.shape[0] if second is not None else 0
-    h2 = torch.empty(n_nodes, H2, dtype=F32, device=x.device) if second is not None else None
-    rc = lib().mdx_egnn_node_inputs(ptr(x, F32, "x"), ptr(k_vectors, F32, "k_vectors"), n_k, ptr(sigma, F32, "sigma"), N,
-                                    ptr(atom_types, I64, "atom_types"), ptr(emb_weight, F32, "emb_weight"),
-                                    ptr(emb_bias, F32, "emb_bias"), F, H, n_nodes, ptr(z, F32, "z"), ptr(h, F32, "h"),
-                                    ptr(w2, F32, "second_weight"), ptr(b2, F32, "second_bias"), H2, ptr(h2, F32, "second_out"),
-                                    stream_handle())
-    check(rc, "mdx_egnn_node_inputs")
+    if memo is not None:
+        z, h, h2 = memo.grid_z, memo.grid_h, memo.grid_proj
+        assert second is not None and tuple(z.shape) == (n_nodes, 2 * n_k) and tuple(h.shape) == (n_nodes, H) and \
+            tuple(h2.shape) == (n_nodes, H2)
+    else:
+        z = torch.empty(n_nodes, 2 * n_k, dtype=F32, device=x.device)
+        h = torch.empty(n_nodes, H, dtype=F32, device=x.device)
+        h2 = torch.empty(n_nodes, H2, dtype=F32, device=x.device) if second is not None else None
+    rc = lib().mdx_egnn_node_inputs_keyed(ptr(x, F32, "x"), ptr(k_vectors, F32, "k_vectors"), n_k, ptr(sigma, F32, "sigma"), N,
+                                          ptr(atom_types, I64, "atom_types"), ptr(emb_weight, F32, "emb_weight"),
+                                          ptr(emb_bias, F32, "emb_bias"), F, H, n_nodes, ptr(z, F32, "z"), ptr(h, F32, "h"),
+                                          ptr(w2, F32, "second_weight"), ptr(b2, F32, "second_bias"), H2,
+                                          ptr(h2, F32, "second_out"), ptr(memo.key if memo is not None else None, I32, "table_key"),
+                                          stream_handle())
+    check(rc, "mdx_egnn_node_inputs_keyed")
     return (z, h) if second is None else (z, h, h2)
 
 

@@ -108,7 +108,8 @@ class E_GCL(nn.Module):
         state.pop("_node_mlp_kept", None)
         state.pop("_node_chain_kept", None)
         state.pop("_activation_scales", None)
-        state.pop("_table_workspace", None)
+        state.pop("_table_memos", None)
+        state.pop("_table_memo_used", None)
         state.pop("table_worst", None)
         return state
 
@@ -128,16 +129,48 @@ class E_GCL(nn.Module):
         activation exponents for the split-f16 kernels (device-side, no host read)."""
         for scales in self.__dict__.get("_activation_scales", {}).values():
             scales.adapt()
+        self.reset_table_memos()
 
     def begin_f16_range_fallback(self):
         """Before the exact-f32 pass of a fallback: forget the maxima earlier f32 launches have left."""
         for scales in self.__dict__.get("_activation_scales", {}).values():
             scales.maxima.zero_()
+        self.reset_table_memos()       # (a skipped build would also skip its share of the maxima)
 
     def reset_f16_range(self):
         """Back to the default activation exponents (and no collected maxima): what a freshly built layer has."""
         for scales in self.__dict__.get("_activation_scales", {}).values():
             scales.reset()
+        self.reset_table_memos()
+
+    def table_memo(self, pack, n_classes: int, n_even: int, embedding_width: int, coord_dimension: int, device, stamp):
+        """The kernels.EgnnTableMemo of this layer as a first graph layer: one per device, precision and grid shape, kept (a
+        captured iteration holds its pointers).  `stamp`: whatever the table's arithmetic depends on besides sigma and the
+        activation exponents -- this layer's pack is added here; when it differs from the stamp of the last call, the key is
+        reset (a fill on the stream)."""
+        from .. import kernels
+        memos = self.__dict__.setdefault("_table_memos", {})
+        key = (pack.precision, n_classes, n_even, pack.hidden, embedding_width, coord_dimension, str(device))
+        memo = memos.get(key)
+        if memo is None:
+            memo = memos[key] = kernels.EgnnTableMemo(n_classes, n_even, pack.hidden, embedding_width, coord_dimension, device)
+        stamp = (self._chain[0], stamp)
+        if memo.stamp != stamp or self.__dict__.get("_table_memo_used") is not memo:
+            # (also after a forward of another precision: the switch to "f32" and back around a range report)
+            if memo.stamp is not None:
+                memo.reset()
+            memo.stamp = stamp
+            self._table_memo_used = memo
+        return memo
+
+    def table_builds(self) -> int:
+        """Distance tables built so far by this layer, over all its memos (host reads: tests and evidence)."""
+        return sum(memo.builds() for memo in self.__dict__.get("_table_memos", {}).values())
+
+    def reset_table_memos(self):
+        """Forget every kept distance table (the activation exponents or maxima changed, or the caller wants a fresh build)."""
+        for memo in self.__dict__.get("_table_memos", {}).values():
+            memo.reset()
 
     def _messages(self, h: torch.Tensor, edge_index: torch.Tensor, radial: torch.Tensor, fused: bool) -> torch.Tensor:
         first = self.message_mlp[0]
@@ -324,7 +357,7 @@ class E_GCL(nn.Module):
     def forward(self, h: torch.Tensor, edge_index: torch.Tensor, coord: torch.Tensor,
                 degree: Optional[torch.Tensor] = None, offsets: Optional[torch.Tensor] = None,
                 n_edges: Optional[torch.Tensor] = None, node_proj: Optional[torch.Tensor] = None,
-                next_layer: Optional["E_GCL"] = None, table=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                next_layer: Optional["E_GCL"] = None, table=None, coords_only: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
         """node_proj: this layer's per-node projections [n_nodes, 2H], when the previous layer's node kernel has already
         computed them; next_layer: the graph layer that follows (its projections are then computed by this layer's node
         kernel and left in self._next_proj).
@@ -333,7 +366,11 @@ class E_GCL(nn.Module):
         on the device when edge_index is a capacity-sized list whose first n_edges rows are the edges (fused chain only);
         table: kernels.EgnnTable when the caller guarantees what the layer's per-edge output on a distance grid needs (one
         value of h per class, the coordinates a torus uplift): the edge chain then runs on the grid and the edges are
-        interpolated from it (_table_gather)."""
+        interpolated from it (_table_gather).
+        coords_only: the caller reads the coordinates alone (the last graph layer of a forward whose atom-type logits nobody
+        reads: its h feeds the classification head only).  Where the layer runs the fused chain at full width without the
+        attention gate, the message sums are then not gathered and the node MLP is not launched: (None, coord_out), the same
+        bits in coord_out.  Everywhere else the flag is ignored."""
         row, col = edge_index[:, 0], edge_index[:, 1]
         if degree is None:
             degree = torch.bincount(row, minlength=h.shape[0])
@@ -345,7 +382,7 @@ class E_GCL(nn.Module):
             pack = self._edge_chain_pack()
             if pack is not None:
                 return self._forward_edge_chain(pack, h, edge_index, coord, degree, offsets, n_edges, node_proj, next_layer,
-                                                table)
+                                                table, coords_only)
         assert n_edges is None, "a capacity-sized edge list needs the fused edge chain in every layer"
         count = degree.clamp(min=1).to(h.dtype).unsqueeze(1)      # (the reference DIVIDES by the count: egnn_utils.py:66-68)
 
@@ -392,21 +429,20 @@ class E_GCL(nn.Module):
         or sigma is not uniform) and the interpolating gather.  Fixed sizes, no host read: capture-safe."""
         from .. import kernels
         _, grid_coord, grid_edges = kernels.egnn_table_grid(table.n_classes, table.n_even, coord.shape[1], coord.device)
-        values, scalars = kernels.egnn_edge_chain(pack, table.grid_proj, grid_coord, grid_edges, status=self.status_word)
-        key = (table.n_classes, pack.hidden, str(coord.device))
-        if getattr(self, "_table_workspace", (None,))[0] != key:
-            # (zero-filled once; every check leaves it zeroed)
-            self._table_workspace = (key, torch.zeros(table.n_classes ** 2 * (pack.hidden + 2), dtype=torch.int32,
-                                                      device=coord.device))
-            self.table_worst = torch.zeros(1, dtype=torch.float32, device=coord.device)
-        kernels.egnn_table_check(values, scalars, table.n_classes, table.n_even, table.sigma, self._table_workspace[1],
-                                 worst=self.table_worst, status=self.status_word)
+        memo = table.memo
+        # the table kept on the device: the chain and the midpoint check return at once while the memo's key holds this forward's
+        # sigma; the uniform-sigma check runs regardless (kernels.EgnnTableMemo)
+        values, scalars = kernels.egnn_edge_chain(pack, memo.grid_proj, grid_coord, grid_edges, status=self.status_word,
+                                                  memo=memo, sigma=table.sigma)
+        self.table_worst = memo.worst
+        kernels.egnn_table_check(values, scalars, table.n_classes, table.n_even, table.sigma, memo.workspace,
+                                 worst=memo.worst, status=self.status_word, key=memo.key)
         return kernels.egnn_table_gather(values, scalars, table.n_classes, table.n_even, table.atom_types, offsets, degree,
                                          self.message_mean, left, coord, edge_index, self.coords_mean,
                                          flags=self._coord_flags(), status=self.status_word)
 
     def _forward_edge_chain(self, pack, h, edge_index, coord, degree, offsets, n_edges=None, node_proj=None, next_layer=None,
-                            table=None):
+                            table=None, coords_only=False):
         """E_GCL.forward with the per-edge work in one MFMA kernel: node projections (library GEMM, per node) -> fused
         chain -> the two sorted-segment reductions -> node MLP.  With `table` (and table_applies) the per-edge chain and the
         node gather are _table_gather."""
@@ -430,6 +466,12 @@ class E_GCL(nn.Module):
                    else kernels.segment_rows(messages, offsets, degree, self.message_mean))
             node_in = torch.cat([h, agg[:, :pack.message_width]], dim=1)
         elif in_kernel and h.shape[1] == messages.shape[1] and coord.shape[1] <= 8:
+            if coords_only and not self.attention:
+                # the coordinate half of the node gather alone (the same launch with the message half switched off: the same
+                # butterfly, the same bits); no node MLP
+                return kernels.egnn_node_gather(None, edge_index.shape[0], offsets, degree, self.message_mean, None, edge_scalar,
+                                                coord, edge_index, self.coords_mean, flags=self._coord_flags())
+
             def gather(left):
                 return kernels.egnn_node_gather(messages, edge_index.shape[0], offsets, degree, self.message_mean, left,
                                                 edge_scalar, coord, edge_index, self.coords_mean, flags=self._coord_flags())
@@ -504,13 +546,15 @@ class EGNN(nn.Module):
                 message_agg=message_agg, tanh=tanh))
 
     def forward(self, h: torch.Tensor, edges: torch.Tensor, x: torch.Tensor, degree=None, embedded: bool = False,
-                first_proj: Optional[torch.Tensor] = None, classify: bool = True, first_table=None) -> AXL:
+                first_proj: Optional[torch.Tensor] = None, classify: bool = True, first_table=None,
+                coords_only: bool = False) -> AXL:
         """degree: None (a caller's own edge list, any order), the edge count per node [n_nodes] of a list sorted by source,
         or the triple (degree, offsets, n_edges) of a capacity-sized list (utils/neighbors.get_edges_static).
         embedded: h is already embedding_in(node features) (kernels.egnn_node_inputs); first_proj: the first graph layer's
         per-node projections [n_nodes, 2H] of that h, when the caller has them.  classify=False: A is the last layer's h (the
         caller applies node_classification_layer: kernels.egnn_outputs) and L is None.  first_table: kernels.EgnnTable for the
-        first graph layer (E_GCL.forward's `table`)."""
+        first graph layer (E_GCL.forward's `table`).  coords_only (with classify=False): the caller reads X alone -- the last
+        graph layer gets E_GCL.forward's `coords_only`, and A is None when that layer could leave its node path out."""
         emb = self.embedding_in
         if embedded:
             assert h.shape[1] == emb.out_features
@@ -537,7 +581,7 @@ class EGNN(nn.Module):
         for k, layer in enumerate(self.graph_layers):
             following = self.graph_layers[k + 1] if k + 1 < len(self.graph_layers) else None
             h, x = layer(h, edges, x, degree, offsets, n_edges, node_proj=proj, next_layer=following,
-                         table=first_table if k == 0 else None)
+                         table=first_table if k == 0 else None, coords_only=coords_only and not classify and following is None)
             proj = layer.__dict__.pop("_next_proj", None)       # left there by the layer's node kernel, if it computed them
         if not classify:
             return AXL(A=h, X=x, L=None)

@@ -125,6 +125,17 @@ class EGNNScoreNetwork(ScoreNetwork):
         # MDX_STATUS_EGNN_TABLE recomputes that iteration on the per-edge chain and sets "off".
         self.first_layer_table = "auto"
         self.sigma_uniform_hint = False
+        # The table depends on sigma, the weights and the activation exponents only, and a sampler runs three consecutive
+        # forwards at one sigma: the table stays on the device under a key (the bits of its sigma) and the kernels of a build
+        # return at once while the key matches (kernels.EgnnTableMemo).  False: the key is reset before every forward -- every
+        # forward builds, as before the table was kept.
+        self.first_layer_table_reuse = True
+        # A caller that will not read the atom-type logits of a forward says so (network_hooks.logits_unread sets
+        # logits_unread_hint: the sampler's corrector steps).  In the last graph layer the node features feed the
+        # classification head only, so that forward leaves out the layer's message gather and node MLP and the head, and
+        # returns A = None; X keeps its bits.  False: the hint is ignored.
+        self.skip_unread_logits = True
+        self.logits_unread_hint = False
         self.egnn = self._make_egnn(hp)
 
     def __getstate__(self):
@@ -165,6 +176,10 @@ class EGNNScoreNetwork(ScoreNetwork):
         for layer in self.egnn.graph_layers:
             layer.reset_f16_range()
 
+    def table_builds(self) -> int:
+        """How many first-layer distance tables have been built so far (the device counters of the kept tables; host reads)."""
+        return self.egnn.graph_layers[0].table_builds() if len(self.egnn.graph_layers) else 0
+
     def check_status(self):
         """Raise for any MDX_STATUS_* bit the forward passes have collected (one host read); clears the word."""
         if self.graph_status is not None:
@@ -175,7 +190,7 @@ class EGNNScoreNetwork(ScoreNetwork):
 
     def _impose_non_mask_atomic_type_prediction(self, output: AXL):
         """The MASK logit is forced to -inf (score_network.py:183-185) -- already done by mdx_egnn_outputs on the fused path."""
-        if not getattr(output.A, "_mdx_mask_imposed", False):
+        if output.A is not None and not getattr(output.A, "_mdx_mask_imposed", False):
             super()._impose_non_mask_atomic_type_prediction(output)
 
     def _first_projection_of_inputs(self):
@@ -207,9 +222,12 @@ class EGNNScoreNetwork(ScoreNetwork):
         mode = self.first_layer_table
         if mode not in ("auto", "on", "off"):
             raise ValueError(f"first_layer_table should be auto, on or off. Got {mode}")
+        layer = self.egnn.graph_layers[0]
+        if mode != self.__dict__.get("_table_mode_seen", mode):
+            layer.reset_table_memos()                   # (a change of first_layer_table: the next table forward builds)
+        self._table_mode_seen = mode
         if mode == "off" or (mode == "auto" and not self.sigma_uniform_hint):
             return None
-        layer = self.egnn.graph_layers[0]
         if not layer.table_applies(layer._edge_chain_pack(), h, z):
             return None
         n_classes = self.num_atom_types + 1
@@ -223,10 +241,16 @@ class EGNNScoreNetwork(ScoreNetwork):
             grid_x = self._table_grid_x = torch.zeros(1, G, 3, dtype=torch.float32, device=z.device)
         sigma = sigma.to(device=z.device, dtype=torch.float32).reshape(-1).contiguous()
         emb = self.egnn.embedding_in
+        # the memo's stamp: the inputs of the grid's node projections (the layer adds its own pack) -- a change resets the key
+        stamp = tuple((t.data_ptr(), t._version) for t in (emb.weight, emb.bias, *second))
+        memo = layer.table_memo(layer._edge_chain_pack(), n_classes, n_even, emb.out_features, z.shape[1], z.device, stamp)
+        if not self.first_layer_table_reuse:
+            memo.reset()
         _, _, grid_proj = kernels.egnn_node_inputs(grid_x, k_vectors.contiguous(), sigma, classes.reshape(1, G),
-                                                   emb.weight.detach().contiguous(), emb.bias.detach().contiguous(), second=second)
+                                                   emb.weight.detach().contiguous(), emb.bias.detach().contiguous(), second=second,
+                                                   memo=memo)
         return kernels.EgnnTable(grid_proj=grid_proj, sigma=sigma, atom_types=atom_types.reshape(-1).long().contiguous(),
-                                 n_classes=n_classes, n_even=n_even)
+                                 n_classes=n_classes, n_even=n_even, memo=memo)
 
     def _make_egnn(self, hp):
         return EGNN(
@@ -324,6 +348,9 @@ class EGNNScoreNetwork(ScoreNetwork):
         return self._static_edge_list_fits(batch_size, number_of_atoms, torch.device(device))
 
     def _forward_unchecked(self, batch: Dict[AnyStr, torch.Tensor], conditional: bool = False) -> AXL:
+        """A is None when the caller has said that it will not read the logits (logits_unread_hint, with skip_unread_logits)
+        and the last graph layer could leave its node path out (models/egnn.py E_GCL.forward, `coords_only`); any other shape
+        or path ignores the hint and returns the logits."""
         comp = batch[NOISY_AXL_COMPOSITION]
         x = comp.X
         bsz, n, d = x.shape
@@ -352,7 +379,10 @@ class EGNNScoreNetwork(ScoreNetwork):
             if head.out_features <= 8 and head.in_features % 4 == 0 and comp.L.dtype == torch.float32:
                 # classification layer (MASK logit at -inf), scores and the zero lattice output: one launch
                 out = self.egnn(h=h, edges=edges, x=z, degree=degree, embedded=True, first_proj=first_proj, classify=False,
-                                first_table=table)
+                                first_table=table, coords_only=self.skip_unread_logits and self.logits_unread_hint)
+                if out.A is None:
+                    scores = kernels.egnn_scores(z, out.X.contiguous(), k_vectors.contiguous())
+                    return AXL(A=None, X=scores.reshape(bsz, n, d), L=torch.zeros_like(comp.L))
                 scores, logits, zeros = kernels.egnn_outputs(
                     z, out.X.contiguous(), k_vectors.contiguous(), out.A.contiguous(), head.weight.detach().contiguous(),
                     head.bias.detach().contiguous(), self.num_atom_types, comp.L.numel())

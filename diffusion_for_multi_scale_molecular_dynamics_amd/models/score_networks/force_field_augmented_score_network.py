@@ -49,7 +49,7 @@ class ForceFieldAugmentedScoreNetwork(torch.nn.Module):
     # lacks is absent here too (hasattr is false, and a set is dropped), so that the hooks' defaults for an absent name --
     # None, "off", a no-op -- mean what they would mean on the wrapped network.  graph_status, check_status and capture_safe
     # are written out below: they also answer for the pseudo-force kernel.
-    FORWARDED = ("edge_chain_precision", "sigma_uniform_hint", "first_layer_table", "adapt_f16_range",
+    FORWARDED = ("edge_chain_precision", "sigma_uniform_hint", "logits_unread_hint", "first_layer_table", "adapt_f16_range",
                  "begin_f16_range_fallback", "reset_f16_range")
 
     def __getattr__(self, name):

@@ -584,7 +584,9 @@ MDX_API int mdx_segment_combine(const float* pieces, int64_t n_edges, const int6
  * with coord_diff, the coordinate residual, torch.cat([h, agg])): out = [left | message sums] (or the sums alone),
  * coord_out[i,:] = coord[i,:] + (1/degree_i if mean_coords) sum_e (coord[i,:] - coord[dst_e,:]) edge_scalar[e].  The node's
  * edges are dealt to the lanes of one wavefront and reduced by a butterfly: fixed order, no atomics.  coord_dimension <= 8.
- * coord_flags: MDX_EGNN_COORD_* bits (0 for the plain layer). */
+ * coord_flags: MDX_EGNN_COORD_* bits (0 for the plain layer).
+ * pieces = left = out = NULL: the coordinate half alone -- coord_out with the same bits, nothing else read or written (the
+ * last graph layer of a forward whose atom-type logits nobody reads: its node features feed the classification head only). */
 MDX_API int mdx_egnn_node_gather(const float* pieces, int64_t n_edges, const int64_t* offsets, const int64_t* degree,
                                  int64_t n_nodes, int H, int mean_messages, const float* left, float* out,
                                  const float* edge_scalar, const float* coord, int coord_dimension, const int64_t* edges,
@@ -608,6 +610,32 @@ MDX_API int mdx_egnn_node_gather(const float* pieces, int64_t n_edges, const int
 MDX_API int mdx_egnn_table_check(const float* table, const float* table_scalar, int H, int n_classes, int n_even,
                                  const float* sigma, int64_t n_sigma, float tolerance, uint32_t* workspace, float* worst_out,
                                  uint32_t* status, mdx_stream_t stream);
+/* The table memoised on the device.  It depends on sigma, the weights and the activation exponents only, and a sampler runs
+ * three consecutive forwards at one sigma, so the caller keeps `table`, `table_scalar` and the grid's node_proj in buffers of
+ * its own beside a KEY RECORD `table_key`: device, uint32 [2] = { the bits of the sigma the table in memory was built at
+ * (MDX_EGNN_TABLE_NO_KEY: none), the number of builds so far (it only goes up) }.  Each kernel of a build first compares
+ * table_key[0] with the bits of this forward's sigma[0] and returns at once when they agree (a NaN sigma never agrees): the
+ * launches stay where they are -- in a captured graph too -- and only their work goes.
+ *   mdx_egnn_node_inputs_keyed / mdx_egnn_edge_chain_keyed: the unkeyed calls with that early return (table_key nullable: the
+ *     unkeyed call; the chain: MDX_EGNN_MESSAGES_ROWS without attention only).
+ *   mdx_egnn_table_check_keyed: the midpoint check only when a build has happened, the uniform-sigma check ALWAYS; writes the key
+ *     last -- the bits of sigma[0] and the counter + 1 when the build passed, MDX_EGNN_TABLE_NO_KEY when it failed (the next
+ *     forward then builds and reports again).
+ * The caller resets table_key[0] to MDX_EGNN_TABLE_NO_KEY (a fill on the stream) whenever something else the table depends on
+ * changes. */
+#define MDX_EGNN_TABLE_NO_KEY 0x7fc00000u
+MDX_API int mdx_egnn_node_inputs_keyed(const float* x, const float* k_vectors, int n_k, const float* sigma,
+                                       int atoms_per_structure, const int64_t* atom_types, const float* emb_weight,
+                                       const float* emb_bias, int n_features, int H, int64_t n_nodes, float* z_out, float* h_out,
+                                       const float* second_weight, const float* second_bias, int second_width, float* second_out,
+                                       const uint32_t* table_key, mdx_stream_t stream);
+MDX_API int mdx_egnn_edge_chain_keyed(const mdx_egnn_chain_t* chain_host, const float* node_proj, const float* coord,
+                                      int coord_dimension, const int64_t* edges, int64_t n_edges, const int64_t* n_edges_dev,
+                                      float* messages_out, float* edge_scalar_out, uint32_t* status, const uint32_t* table_key,
+                                      const float* sigma, mdx_stream_t stream);
+MDX_API int mdx_egnn_table_check_keyed(const float* table, const float* table_scalar, int H, int n_classes, int n_even,
+                                       const float* sigma, int64_t n_sigma, float tolerance, uint32_t* workspace,
+                                       float* worst_out, uint32_t* status, uint32_t* table_key, mdx_stream_t stream);
 MDX_API int mdx_egnn_table_gather(const float* table, const float* table_scalar, int H, int n_classes, int n_even,
                                   float inv_spacing, const int64_t* atom_types, const int64_t* offsets, const int64_t* degree,
                                   int64_t n_nodes, int mean_messages, const float* left, float* out, const float* coord,
