@@ -18,6 +18,7 @@ MDX_PREDICTOR, MDX_CORRECTOR = 0, 1
 STATUS_CUTOFF_TOO_LARGE, STATUS_MASK_AT_LAST_STEP, STATUS_EGNN_F16_RANGE, STATUS_GRAPH_CAPACITY = 1, 2, 4, 8
 STATUS_EGNN_TABLE = 16
 STATUS_SW_NEIGHBOURS, STATUS_SW_ATOM_TYPE = 32, 64     # mdx_stillinger_weber_energy_forces
+STATUS_ANALYTICAL_SIGMA, STATUS_ANALYTICAL_COORDINATES = 128, 256     # mdx_analytical_score, the wrapped-Gaussian functions
 EGNN_COORD_NORMALIZE, EGNN_COORD_TANH = 1, 2      # MDX_EGNN_COORD_* (coord_flags of mdx_egnn_node_gather / _coord_aggregate)
 EGNN_CHAIN_MAX_LAYERS = 16
 MAX_CLASSES = 8
@@ -39,6 +40,7 @@ ABI_SYMBOLS = (
     "mdx_egnn_table_check", "mdx_egnn_table_gather", "mdx_egnn_node_inputs_keyed", "mdx_egnn_edge_chain_keyed",
     "mdx_egnn_table_check_keyed", "mdx_rng_fill", "mdx_math_probe",
     "mdx_stillinger_weber_workspace_doubles", "mdx_stillinger_weber_energy_forces",
+    "mdx_wrapped_gaussian_sigma_normalized_score", "mdx_log_wrapped_gaussians", "mdx_analytical_score",
 )
 MLP_MAX_HIDDEN = 8
 # options of mdx_mlp_pc_sample (include/mdx_hip.h)
@@ -190,6 +192,12 @@ def _declare(L):
     L.mdx_stillinger_weber_workspace_doubles.argtypes = [i64, i32, i32]
     L.mdx_stillinger_weber_energy_forces.restype = i32
     L.mdx_stillinger_weber_energy_forces.argtypes = [vp, vp, i32, vp, vp, i32, i64, i32, i32, vp, i64, vp, vp, vp, vp]
+    L.mdx_wrapped_gaussian_sigma_normalized_score.restype = i32
+    L.mdx_wrapped_gaussian_sigma_normalized_score.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp]
+    L.mdx_log_wrapped_gaussians.restype = i32
+    L.mdx_log_wrapped_gaussians.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp]
+    L.mdx_analytical_score.restype = i32
+    L.mdx_analytical_score.argtypes = [vp, vp, i32, vp, f64, i32, i32, i64, i32, i32, vp, vp, vp, vp]
     L.mdx_mlp_forward.restype = i32
     L.mdx_mlp_forward.argtypes = [C.POINTER(Mlp), vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
     L.mdx_mlp_pc_sample.restype = i32

@@ -2194,6 +2194,9 @@ const char* mdx_status_string(int status)
         case MDX_ERR_INVALID_ARG: return "invalid argument";
         case MDX_ERR_UNSUPPORTED: return "unsupported size or option";
         case MDX_ERR_HIP: return "HIP runtime error at launch";
+        // the two bits a caller of the analytical score functions reads back from its status word
+        case MDX_STATUS_ANALYTICAL_SIGMA: return "All values of sigma should be larger than zero.";
+        case MDX_STATUS_ANALYTICAL_COORDINATES: return "the relative coordinates should all be in [0, 1)";
         default: return "unknown status";
     }
 }

@@ -83,7 +83,7 @@ class AdaptiveCorrectorGenerator(LangevinGenerator):
         kernels.fill_time_sigma(sched, MDX_CORRECTOR, index_i, d_index, time_t, sigma_t)
         predictions = self._get_model_predictions(comp, time_t, sigma_t, forces)
         score_x = predictions.X.contiguous()
-        score_l = None if fixed else predictions.L.contiguous()
+        score_l = self._lattice_score(predictions, comp)
         workspace, totals, weights = self._step_buffers(batch, device)
         rng = self._rng(1 + corrector_number)
         sync = self._sync_across_ranks()
@@ -193,8 +193,9 @@ class AdaptiveCorrectorGenerator(LangevinGenerator):
         if not self.use_fixed_lattice_parameters:
             sigma_n = sigma / (n ** (1 / d))
             z_used = self._draw_lattice_gaussian_sample(batch).to(device).contiguous()   # the reference's 2nd draw
-            eps_l = self._step_size(sigma_n, predictions.L, z_lattice, coordinates=False)
-            lattice = kernels.lattice_parameters_update(lattice.contiguous(), predictions.L.contiguous(), z_used,
+            score_l = self._lattice_score(predictions, composition_i)
+            eps_l = self._step_size(sigma_n, score_l, z_lattice, coordinates=False)
+            lattice = kernels.lattice_parameters_update(lattice.contiguous(), score_l, z_used,
                                                         weights=torch.stack([eps_l, torch.sqrt(2 * eps_l), sigma_n]).float())
         out = AXL(A=composition_i.A, X=x_out, L=lattice)
         if self.record_corrector:

@@ -315,6 +315,17 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
         with hooks.uniform_sigma(self.axl_network):        # (the loop fills one sigma for the whole batch)
             return self.axl_network(batch, conditional=False)
 
+    def _lattice_score(self, predictions: AXL, composition: AXL) -> Optional[torch.Tensor]:
+        """The lattice score the update kernels read: None under fixed lattice parameters; otherwise it must have the shape of
+        the lattice parameters (a network without a lattice score -- the analytical one returns zeros [B, N, d], as in the
+        reference, whose update cannot broadcast them either -- is refused rather than read as [B, d (d + 1) / 2])."""
+        if self.use_fixed_lattice_parameters:
+            return None
+        if predictions.L.shape != composition.L.shape:
+            raise MdxError(f"the score network's lattice output has shape {tuple(predictions.L.shape)}, the lattice parameters "
+                           f"{tuple(composition.L.shape)}: this network can only sample with use_fixed_lattice_parameters=True")
+        return predictions.L.contiguous()
+
     # ---------------------------------------------------------------------------------------------------------
     # one step = network forward + ONE fused update kernel
     # ---------------------------------------------------------------------------------------------------------
@@ -375,7 +386,7 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
         kernels.pc_step_update(sched, mode, index_i, d_index, self._flags(update_types),
                                a_in if update_types else None, x, composition.L, logits,
                                predictions.X.contiguous(),
-                               None if self.use_fixed_lattice_parameters else predictions.L.contiguous(),
+                               self._lattice_score(predictions, composition),
                                z, gumbel, u, z_lattice, self._rng(draw_offset),
                                a_out if update_types else None, x_out, l_out, self._status)
         if self.record_atom_type_update and update_types:

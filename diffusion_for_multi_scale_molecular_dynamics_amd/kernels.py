@@ -442,6 +442,95 @@ def stillinger_weber_energy_forces(relative_coordinates, lattice_parameters, ato
 
 
 # ----------------------------------------------------------------------------------------------------------------
+# analytical score network (csrc/mdx_analytical.hip)
+# ----------------------------------------------------------------------------------------------------------------
+ANALYTICAL_MAX_ATOMS, ANALYTICAL_MAX_PERMUTED_ATOMS = 1024, 8
+
+
+def _device_only(what: str, **tensors):
+    for name, t in tensors.items():
+        if t is not None and not t.is_cuda:
+            raise _hip.MdxError(f"{name} lives on {t.device}: {what} runs on the GPU only (no CPU fallback)")
+
+
+def raise_analytical_bits(word: int):
+    """The reference's two value assertions (score/wrapped_gaussian_score.py:155-159) for the bits of a status word read earlier."""
+    if word & _hip.STATUS_ANALYTICAL_SIGMA:
+        raise AssertionError("All values of sigma should be larger than zero.")
+    if word & _hip.STATUS_ANALYTICAL_COORDINATES:
+        raise AssertionError("the relative coordinates should all be in [0, 1)")
+
+
+def raise_analytical_status(status: torch.Tensor):
+    """One host read of a status word the analytical kernels reported into: their bits are cleared, then raised."""
+    both = _hip.STATUS_ANALYTICAL_SIGMA | _hip.STATUS_ANALYTICAL_COORDINATES
+    word = int(status.item())
+    if word & both:
+        status.bitwise_and_(~both)
+    raise_analytical_bits(word)
+
+
+def wrapped_gaussian_sigma_normalized_score(relative_coordinates, sigmas, kmax: int, coordinates_bounded: bool = True,
+                                            status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sigma x score of the wrapped Gaussian, elementwise over f32 tensors of one shape (mdx_wrapped_gaussian_sigma_normalized_score):
+    binary64 inside, the reference's three formulas and truncation.  Invalid values give NaN and their bit in `status`."""
+    _device_only("the wrapped-Gaussian score", relative_coordinates=relative_coordinates, sigmas=sigmas, status=status)
+    if relative_coordinates.shape != sigmas.shape:
+        raise ValueError("relative_coordinates and sigmas must have the same shape")
+    out = torch.empty_like(relative_coordinates)
+    check(lib().mdx_wrapped_gaussian_sigma_normalized_score(ptr(relative_coordinates, F32, "relative_coordinates"),
+                                                            ptr(sigmas, F32, "sigmas"), relative_coordinates.numel(), int(kmax),
+                                                            int(bool(coordinates_bounded)), ptr(out, F32, "out"),
+                                                            ptr(status, I32, "status"), stream_handle()),
+          "mdx_wrapped_gaussian_sigma_normalized_score")
+    return out
+
+
+def log_wrapped_gaussians(relative_coordinates, sigmas, kmax: int, row_length: int,
+                          status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Log wrapped Gaussians of f32 tensors of one shape, summed over rows of `row_length` trailing elements: f32
+    [numel / row_length] (mdx_log_wrapped_gaussians)."""
+    _device_only("the log wrapped Gaussian", relative_coordinates=relative_coordinates, sigmas=sigmas, status=status)
+    if relative_coordinates.shape != sigmas.shape:
+        raise ValueError("relative_coordinates and sigmas must have the same shape")
+    if row_length < 1 or relative_coordinates.numel() % row_length:
+        raise ValueError(f"row_length {row_length} does not divide {relative_coordinates.numel()} elements")
+    rows = relative_coordinates.numel() // row_length
+    out = torch.empty(rows, dtype=F32, device=relative_coordinates.device)
+    check(lib().mdx_log_wrapped_gaussians(ptr(relative_coordinates, F32, "relative_coordinates"), ptr(sigmas, F32, "sigmas"), rows,
+                                          int(row_length), int(kmax), ptr(out, F32, "out"), ptr(status, I32, "status"),
+                                          stream_handle()), "mdx_log_wrapped_gaussians")
+    return out
+
+
+def analytical_score(relative_coordinates, sigmas, equilibrium_relative_coordinates, sigma_d_square: float, kmax: int,
+                     use_permutation_invariance: bool, with_probabilities: bool = False, status: Optional[torch.Tensor] = None):
+    """(sigma-normalised score f32 [B,N,D], probabilities f32 [B] or None) of the analytical score network (mdx_analytical_score):
+    relative_coordinates f32 [B,N,D]; sigmas f32 [B] (one per structure) or [B,N,D] (one per element); sites f32 [N,D].  One
+    kernel, no host read: a structure with an invalid sigma or coordinate holds NaNs and its bit is OR-ed into `status`."""
+    _device_only("the analytical score", relative_coordinates=relative_coordinates, sigmas=sigmas,
+                 equilibrium_relative_coordinates=equilibrium_relative_coordinates, status=status)
+    B, N, D = relative_coordinates.shape
+    if equilibrium_relative_coordinates.shape != (N, D):
+        raise ValueError(f"equilibrium_relative_coordinates has shape {tuple(equilibrium_relative_coordinates.shape)}, expected {(N, D)}")
+    if sigmas.shape == relative_coordinates.shape:
+        per_element = 1
+    elif sigmas.numel() == B:
+        per_element = 0
+    else:
+        raise ValueError(f"sigmas has shape {tuple(sigmas.shape)}: expected [{B}] or {tuple(relative_coordinates.shape)}")
+    dev = relative_coordinates.device
+    scores = torch.empty(B, N, D, dtype=F32, device=dev)
+    probabilities = torch.empty(B, dtype=F32, device=dev) if with_probabilities else None
+    check(lib().mdx_analytical_score(ptr(relative_coordinates, F32, "relative_coordinates"), ptr(sigmas, F32, "sigmas"), per_element,
+                                     ptr(equilibrium_relative_coordinates, F32, "equilibrium_relative_coordinates"),
+                                     float(sigma_d_square), int(kmax), int(bool(use_permutation_invariance)), B, N, D,
+                                     ptr(scores, F32, "scores"), ptr(probabilities, F32, "probabilities"),
+                                     ptr(status, I32, "status"), stream_handle()), "mdx_analytical_score")
+    return scores, probabilities
+
+
+# ----------------------------------------------------------------------------------------------------------------
 # fused MLP score network
 # ----------------------------------------------------------------------------------------------------------------
 class MlpPack:

@@ -6,7 +6,9 @@ Differences, all additive:
   * the score network comes from `--checkpoint` as in the reference -- the trainer's Lightning checkpoint: rebuilt from the
     hyper-parameters pickled inside it, weights under the prefix `axl_network.` (read without Lightning and without the
     reference package: utils/lightning_checkpoint.py) -- or, additionally, from a bare state_dict together with a `model:
-    score_network:` block in the config, or is randomly initialised with `--random_init_seed` (synthetic benchmarks);
+    score_network:` block in the config, or is randomly initialised with `--random_init_seed` (synthetic benchmarks); an exact
+    network (`architecture: analytical`: no trained weights) is built from the `model: score_network:` block alone when no
+    `--checkpoint` is given;
   * under `torchrun` (one process per GPU) the sub-batches are sharded over the ranks and gathered once (RCCL);
     rank 0 writes the files (`trajectories.pt` holds every rank's recorded sub-batches, in sub-batch order);
   * `oracle: {name: stillinger_weber, sw_coeff_filename: <a LAMMPS .sw file, absolute or relative to the configuration>}` writes
@@ -32,7 +34,8 @@ from .generators.sampling_constraint import read_sampling_constraint
 from .generators.trajectory_initializer import instantiate_trajectory_initializer
 from .models.score_networks.score_network import ScoreNetwork
 from .data.element_types import ElementTypes
-from .models.score_networks.score_network_factory import create_score_network, create_score_network_parameters
+from .models.score_networks.score_network_factory import (EXACT_SCORE_NETWORKS_BY_ARCH, create_score_network,
+                                                          create_score_network_parameters)
 from .noise_schedulers.noise_parameters import NoiseParameters
 from .namespace import AXL, AXL_COMPOSITION
 from .sampling.diffusion_sampling import create_batch_of_samples_sharded
@@ -61,6 +64,16 @@ def global_parameters_of(hyper_params: Dict[AnyStr, Any]) -> Optional[Dict[AnySt
                     elements=hyper_params["elements"])
     out = {key: hyper_params[key] for key in ("elements", "spatial_dimension") if key in hyper_params}
     return out or None
+
+
+def exact_score_network_block(hyper_params: Dict[AnyStr, Any]) -> Optional[Dict[AnyStr, Any]]:
+    """The configuration's `model: score_network:` block when it names an exact architecture (one with no trained weights, which
+    can therefore be built without a checkpoint); None otherwise."""
+    model = hyper_params.get("model")
+    block = model.get("score_network") if isinstance(model, dict) else None
+    if isinstance(block, dict) and block.get("architecture") in EXACT_SCORE_NETWORKS_BY_ARCH:
+        return block
+    return None
 
 
 def get_axl_network(checkpoint_path, hyper_params: Optional[Dict[AnyStr, Any]] = None) -> ScoreNetwork:
@@ -136,6 +149,10 @@ def main(args: Optional[Any] = None, axl_network: Optional[ScoreNetwork] = None)
             torch.manual_seed(args.random_init_seed)
             axl_network = create_score_network(
                 create_score_network_parameters(hyper_params["model"]["score_network"], global_parameters_of(hyper_params))).eval()
+        elif args.checkpoint is None and exact_score_network_block(hyper_params) is not None:
+            # an exact network (`architecture: analytical`) has no trained weights: the `model: score_network:` block is all of it
+            axl_network = create_score_network(
+                create_score_network_parameters(exact_score_network_block(hyper_params), global_parameters_of(hyper_params))).eval()
         else:
             assert args.checkpoint is not None and os.path.exists(args.checkpoint), \
                 f"The path {args.checkpoint} does not exist. Cannot go on."

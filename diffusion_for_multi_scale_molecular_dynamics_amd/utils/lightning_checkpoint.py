@@ -72,7 +72,7 @@ def load_checkpoint(path) -> Dict[str, Any]:
 def score_network_parameters_of(checkpoint: Dict[str, Any]) -> Optional[Any]:
     """The `score_network_parameters` the checkpoint's model was built from, as THIS package's dataclass (rebuilt through its
     constructor: fields this package adds take their defaults), or None when the file holds no hyper-parameters."""
-    from ..models.score_networks.score_network_factory import SCORE_NETWORK_PARAMETERS_BY_ARCH
+    from ..models.score_networks.score_network_factory import lookup_architecture
     hyper = checkpoint.get("hyper_parameters")
     if hyper is None:
         return None
@@ -83,10 +83,10 @@ def score_network_parameters_of(checkpoint: Dict[str, Any]) -> Optional[Any]:
     read = (lambda key: stored.get(key)) if isinstance(stored, dict) else (lambda key: getattr(stored, key, None))
     has = (lambda key: key in stored) if isinstance(stored, dict) else (lambda key: hasattr(stored, key))
     architecture = read("architecture")
-    assert architecture in SCORE_NETWORK_PARAMETERS_BY_ARCH, \
-        f"the checkpoint's score network has architecture {architecture!r}: not implemented here " \
-        f"(choices: {list(SCORE_NETWORK_PARAMETERS_BY_ARCH)})"
-    cls = SCORE_NETWORK_PARAMETERS_BY_ARCH[architecture]
+    found = lookup_architecture(architecture)
+    assert found is not None, \
+        f"the checkpoint's score network has architecture {architecture!r}: not implemented here"
+    cls = found[1]
     return cls(**{f.name: read(f.name) for f in dataclasses.fields(cls) if f.init and has(f.name)})
 
 

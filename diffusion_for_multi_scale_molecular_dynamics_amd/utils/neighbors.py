@@ -36,6 +36,7 @@ def _raise_if_cutoff_too_large(status: torch.Tensor):
                                   "results of this call are invalid -- run the network with edge_chain_precision='f32'")
     if word & STATUS_GRAPH_CAPACITY:
         raise MdxError("radius graph: the edge list outgrew its capacity and the retry did not run (internal error)")
+    kernels.raise_analytical_bits(word)       # the analytical score network's kernel: the reference's two value assertions
 
 
 def embed_in_three_dimensions(cartesian_positions: torch.Tensor, basis_vectors: torch.Tensor, radial_cutoff: float):

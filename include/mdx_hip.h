@@ -49,6 +49,11 @@ extern "C" {
                                             caller's neighbour capacity (its structure's results are NaN, not truncated) */
 #define MDX_STATUS_SW_ATOM_TYPE 64u      /* mdx_stillinger_weber_energy_forces: an atom type outside the parameter table
                                             (MASK included); its structure's results are NaN                           */
+#define MDX_STATUS_ANALYTICAL_SIGMA 128u /* mdx_analytical_score and the wrapped-Gaussian functions: a sigma that is not a
+                                            finite positive number (score/wrapped_gaussian_score.py:155 assert); the
+                                            structure's (element's) results are NaN                                     */
+#define MDX_STATUS_ANALYTICAL_COORDINATES 256u /* the same functions: a relative coordinate outside [0, 1) or not finite
+                                            (score/wrapped_gaussian_score.py:156-159 assert); results NaN likewise      */
 
 #define MDX_MAX_CLASSES 8      /* C supported by the fused atom-type kernels */
 #define MDX_PREDICTOR 0
@@ -356,6 +361,44 @@ MDX_API int mdx_stillinger_weber_energy_forces(const float* relative_coordinates
                                                int n_types, int64_t batch, int number_of_atoms, int neighbour_capacity,
                                                double* workspace, int64_t workspace_doubles, double* energies, double* forces,
                                                uint32_t* status, mdx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Analytical score network (csrc/mdx_analytical.hip): wrapped Gaussians of width sigma_d around equilibrium sites.
+ * Common to the three functions: binary32 inputs are promoted once, everything inside is binary64, every output is rounded
+ * once to binary32; kmax in [0, 64] (the sums run over k in [-kmax, kmax], the reference's truncation), else
+ * MDX_ERR_UNSUPPORTED; status (nullable) receives MDX_STATUS_ANALYTICAL_SIGMA / _COORDINATES and the affected outputs are NaN --
+ * invalid input is reported, never a fault; no float atomics, so a launch (or a hipGraph replay) always gives the same bits. */
+
+/* sigma x score of the wrapped Gaussian, elementwise over n values (score/wrapped_gaussian_score.py:131-419,
+ * get_coordinates_sigma_normalized_score): the reference's three formulas with its truncation -- 1a for sigma <= thr and
+ * u < 0.5, 1b for sigma <= thr and u >= 0.5, the Ewald form for sigma > thr, thr the BINARY32 constant 1 / sqrt(2 pi) the
+ * reference compares with.  (They are different truncations: at small kmax not one converged lattice sum.)
+ * coordinates_bounded != 0: a u outside [0, 1) is reported; 0: only a non-finite one. */
+MDX_API int mdx_wrapped_gaussian_sigma_normalized_score(const float* relative_coordinates, const float* sigmas, int64_t n,
+                                                        int kmax, int coordinates_bounded, float* out, uint32_t* status,
+                                                        mdx_stream_t stream);
+
+/* log of the wrapped Gaussians, summed over rows (score/wrapped_gaussian_score.py:41-92, get_log_wrapped_gaussians):
+ * out[r] = sum over the row_length trailing elements of logsumexp_k(-(u + k)^2 / (2 sigma^2)) - log(sqrt(2 pi) sigma), with
+ * sqrt(2 pi) the binary32 value the reference multiplies by. */
+MDX_API int mdx_log_wrapped_gaussians(const float* relative_coordinates, const float* sigmas, int64_t rows, int row_length,
+                                      int kmax, float* out, uint32_t* status, mdx_stream_t stream);
+
+/* The analytical score network's forward (models/score_networks/analytical_score_network.py:135-298,
+ * get_probabilities_and_normalized_scores): relative_coordinates f32 [batch, N, D]; sigmas f32 [batch] (sigma_per_element 0) or
+ * [batch, N, D] (1); equilibrium_relative_coordinates f32 [N, D]; sigma_normalized_scores f32 [batch, N, D]; probabilities
+ * (nullable) f32 [batch].  With u = wrap(x_n - site_j) (binary64 difference; a fraction that rounds to 1 becomes 0) and
+ * s = sqrt(sigma_d_square + sigma^2), a structure's result is the softmax-weighted sum over the equilibrium arrangements p of
+ * sigma score(u, s) / s with weights log_w[p] = sum_{n, d} log wrapped Gaussian(u, s): ONE arrangement (site n for atom n)
+ * without use_permutation_invariance, all N! assignments of sites to atoms with it -- evaluated from an N x N table of terms,
+ * never from N! copies.  probabilities = sum_p exp(log_w[p]) / (number of arrangements) (0 or inf where binary32 under- or
+ * overflows).  One workgroup per structure, one launch, no host read.
+ * N <= 1024 and D <= 3; with use_permutation_invariance N <= 8; else MDX_ERR_UNSUPPORTED.  A structure holding a sigma that is
+ * not finite and positive, or a coordinate outside [0, 1), gets NaN outputs and its bit in status; the others are unaffected. */
+MDX_API int mdx_analytical_score(const float* relative_coordinates, const float* sigmas, int sigma_per_element,
+                                 const float* equilibrium_relative_coordinates, double sigma_d_square, int kmax,
+                                 int use_permutation_invariance, int64_t batch, int number_of_atoms, int spatial_dimension,
+                                 float* sigma_normalized_scores, float* probabilities, uint32_t* status, mdx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Fused score network: the reference's MLPScoreNetwork (models/score_networks/mlp_score_network.py:54-370,
