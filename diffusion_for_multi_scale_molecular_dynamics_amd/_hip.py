@@ -19,6 +19,8 @@ STATUS_CUTOFF_TOO_LARGE, STATUS_MASK_AT_LAST_STEP, STATUS_EGNN_F16_RANGE, STATUS
 STATUS_EGNN_TABLE = 16
 STATUS_SW_NEIGHBOURS, STATUS_SW_ATOM_TYPE = 32, 64     # mdx_stillinger_weber_energy_forces
 STATUS_ANALYTICAL_SIGMA, STATUS_ANALYTICAL_COORDINATES = 128, 256     # mdx_analytical_score, the wrapped-Gaussian functions
+STATUS_EXCISE_CAPACITY, STATUS_EXCISE_OUTSIDE_BOX, STATUS_EXCISE_CENTRAL_INDEX = 512, 1024, 2048     # mdx_excise_environments
+EXCISE_RADIUS, EXCISE_NEIGHBOURS, EXCISE_MAX_ATOMS = 0, 1, 4096
 EGNN_COORD_NORMALIZE, EGNN_COORD_TANH = 1, 2      # MDX_EGNN_COORD_* (coord_flags of mdx_egnn_node_gather / _coord_aggregate)
 EGNN_CHAIN_MAX_LAYERS = 16
 MAX_CLASSES = 8
@@ -41,6 +43,7 @@ ABI_SYMBOLS = (
     "mdx_egnn_table_check_keyed", "mdx_rng_fill", "mdx_math_probe",
     "mdx_stillinger_weber_workspace_doubles", "mdx_stillinger_weber_energy_forces",
     "mdx_wrapped_gaussian_sigma_normalized_score", "mdx_log_wrapped_gaussians", "mdx_analytical_score",
+    "mdx_repaint_rows_per_sample", "mdx_excise_environments", "mdx_edit_keep_mask",
 )
 MLP_MAX_HIDDEN = 8
 # options of mdx_mlp_pc_sample (include/mdx_hip.h)
@@ -174,6 +177,13 @@ def _declare(L):
     L.mdx_repaint_constrained_rows.restype = i32
     L.mdx_repaint_constrained_rows.argtypes = [C.POINTER(Schedule), i32, vp, vp, vp, vp, i32, vp, vp, Rng, i64, i32,
                                                i32, vp, vp, vp]
+    L.mdx_repaint_rows_per_sample.restype = i32
+    L.mdx_repaint_rows_per_sample.argtypes = [C.POINTER(Schedule), i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, Rng, i64, i32,
+                                              i32, vp, vp, vp]
+    L.mdx_excise_environments.restype = i32
+    L.mdx_excise_environments.argtypes = [vp, vp, i32, i32, vp, i32, i32, f64, i32, i32, vp, i32, vp, vp, vp, vp, vp]
+    L.mdx_edit_keep_mask.restype = i32
+    L.mdx_edit_keep_mask.argtypes = [vp, vp, i32, vp, vp, vp, i32, f64, i64, i32, i32, vp, vp]
     L.mdx_forward_diffusion_step.restype = i32
     L.mdx_forward_diffusion_step.argtypes = [C.POINTER(Schedule), i32, vp, vp, vp, Rng, i64, i32, i32, vp, vp, vp]
     L.mdx_radius_graph_count.restype = i32

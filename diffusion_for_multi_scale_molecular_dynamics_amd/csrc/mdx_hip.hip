@@ -14,6 +14,7 @@
 //   mlp_forward_kernel, mlp_pack_image_kernel, pc_noise_fill_kernel, mlp_pc_sample_kernel
 //                              fused MLP score network and the persistent sampler built on it (one wavefront = one structure)
 //   repaint_rows_kernel    R1  forward-noise + scatter of the constrained rows (F1 + F2 fused)
+//   repaint_rows_per_sample_kernel  R1 with one constraint table per environment of the batch
 //   rng_fill_kernel            Philox draws as arrays
 // 64-wide wavefronts are assumed throughout (gfx950).
 #include <hip/hip_runtime.h>
@@ -2008,10 +2009,43 @@ struct RepaintArgs {
     int64_t* a;
 };
 
+// one constrained row: the known atom (x0, a0) forward-noised to time index `index` and written to atom `at` of the batch
+__device__ __forceinline__ void repaint_row(const RepaintArgs& p, int index, int64_t at, const float* x0, int a0, uint32_t k0,
+                                            uint32_t k1, uint32_t call8, uint32_t draw)
+{
+    const int C = p.C, d = p.d;
+    if (index == 0) {                        // constrained_langevin_generator.py:120-123: no noise at t = 0
+        for (int c = 0; c < d; ++c) p.x[at * d + c] = x0[c];
+        p.a[at] = a0;
+        return;
+    }
+    const int idx = index - 1;               // noising_transform.py:112
+    const float sigma = p.sched.sigma[idx];
+    float z[4];
+    if (!p.z) {
+        const u32x4 r = philox4x32_10((uint32_t)at, call8, draw, MDX_TAG_REPAINT_Z, k0, k1);
+        box_muller(r.v[0], r.v[1], z[0], z[1]);
+        if (d > 2) box_muller(r.v[2], r.v[3], z[2], z[3]);
+    }
+    for (int c = 0; c < d; ++c) {
+        const float zz = p.z ? p.z[at * d + c] : z[c];
+        p.x[at * d + c] = wrap01(x0[c] + sigma * zz);
+    }
+    float uu[MDX_MAX_CLASSES];
+    if (p.u) {
+        for (int c = 0; c < C; ++c) uu[c] = p.u[at * C + c];
+    } else {
+        for (int sub = 0; sub * 4 < C; ++sub) {
+            const u32x4 r = philox4x32_10((uint32_t)at, call8 | (uint32_t)sub, draw, MDX_TAG_REPAINT_U, k0, k1);
+            for (int l = 0; l < 4 && sub * 4 + l < C; ++l) uu[sub * 4 + l] = u01(r.v[l]);
+        }
+    }
+    p.a[at] = noised_atom_type(a0, p.sched.qbar + (int64_t)idx * C * C, C, uu, true);
+}
+
 __global__ __launch_bounds__(kBlock) void repaint_rows_kernel(RepaintArgs p)
 {
     const int index = (p.d_index ? *p.d_index : 0) + p.index_i;
-    const int C = p.C, d = p.d;
     const uint32_t k0 = (uint32_t)p.rng.seed, k1 = (uint32_t)(p.rng.seed >> 32);
     const uint32_t call8 = rng_call(p.rng) << 8;
     const uint32_t draw = (uint32_t)index * p.rng.draw_stride + p.rng.draw_offset;
@@ -2019,36 +2053,32 @@ __global__ __launch_bounds__(kBlock) void repaint_rows_kernel(RepaintArgs p)
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
         const int64_t b = t / p.K;
         const int k = (int)(t - b * p.K);
-        const int64_t row = p.cidx[k];
-        const int64_t at = b * p.N + row;
-        const int a0 = (int)p.ca[k];
-        if (index == 0) {                        // constrained_langevin_generator.py:120-123: no noise at t = 0
-            for (int c = 0; c < d; ++c) p.x[at * d + c] = p.cx[k * d + c];
-            p.a[at] = a0;
-            continue;
-        }
-        const int idx = index - 1;               // noising_transform.py:112
-        const float sigma = p.sched.sigma[idx];
-        float z[4];
-        if (!p.z) {
-            const u32x4 r = philox4x32_10((uint32_t)at, call8, draw, MDX_TAG_REPAINT_Z, k0, k1);
-            box_muller(r.v[0], r.v[1], z[0], z[1]);
-            if (d > 2) box_muller(r.v[2], r.v[3], z[2], z[3]);
-        }
-        for (int c = 0; c < d; ++c) {
-            const float zz = p.z ? p.z[at * d + c] : z[c];
-            p.x[at * d + c] = wrap01(p.cx[k * d + c] + sigma * zz);
-        }
-        float uu[MDX_MAX_CLASSES];
-        if (p.u) {
-            for (int c = 0; c < C; ++c) uu[c] = p.u[at * C + c];
-        } else {
-            for (int sub = 0; sub * 4 < C; ++sub) {
-                const u32x4 r = philox4x32_10((uint32_t)at, call8 | (uint32_t)sub, draw, MDX_TAG_REPAINT_U, k0, k1);
-                for (int l = 0; l < 4 && sub * 4 + l < C; ++l) uu[sub * 4 + l] = u01(r.v[l]);
-            }
-        }
-        p.a[at] = noised_atom_type(a0, p.sched.qbar + (int64_t)idx * C * C, C, uu, true);
+        repaint_row(p, index, b * p.N + p.cidx[k], p.cx + k * p.d, (int)p.ca[k], k0, k1, call8, draw);
+    }
+}
+
+// The same rows from per-ENVIRONMENT tables: sample b belongs to environment e = environment[b] and takes the first counts[e]
+// rows of cx / ca / cidx [E, K, ...] (K = the tables' capacity; the rows past counts[e] are padding and are skipped).  The
+// Philox item stays the atom's position in the whole batch, b N + row: with equal environments this IS repaint_rows_kernel.
+// A row index outside [0, N) or an atom type outside the schedule's classes is skipped too: no table sends an access out of bounds.
+__global__ __launch_bounds__(kBlock) void repaint_rows_per_sample_kernel(RepaintArgs p, const int32_t* environment,
+                                                                         const int32_t* counts, int E)
+{
+    const int index = (p.d_index ? *p.d_index : 0) + p.index_i;
+    const uint32_t k0 = (uint32_t)p.rng.seed, k1 = (uint32_t)(p.rng.seed >> 32);
+    const uint32_t call8 = rng_call(p.rng) << 8;
+    const uint32_t draw = (uint32_t)index * p.rng.draw_stride + p.rng.draw_offset;
+    const int64_t total = p.B * p.K;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = t / p.K;
+        const int k = (int)(t - b * p.K);
+        const int e = environment[b];
+        if (e < 0 || e >= E || k >= counts[e]) continue;
+        const int64_t slot = (int64_t)e * p.K + k;
+        const int64_t row = p.cidx[slot];
+        const int64_t a0 = p.ca[slot];
+        if (row < 0 || row >= p.N || a0 < 0 || a0 >= p.C) continue;
+        repaint_row(p, index, b * p.N + row, p.cx + slot * p.d, (int)a0, k0, k1, call8, draw);
     }
 }
 
@@ -2540,6 +2570,31 @@ int mdx_repaint_constrained_rows(const mdx_schedule_t* sched_host, int index_i, 
     a.x = x_inout; a.a = a_inout;
     hipLaunchKernelGGL(repaint_rows_kernel, dim3(flat_grid(batch * number_of_constraints)), dim3(kBlock), 0,
                        as_stream(stream), a);
+    return launch_status();
+}
+
+int mdx_repaint_rows_per_sample(const mdx_schedule_t* sched_host, int index_i, const int32_t* d_index,
+                                const float* constrained_x, const int64_t* constrained_a, const int64_t* constrained_indices,
+                                const int32_t* counts, int number_of_environments, int capacity,
+                                const int32_t* sample_environment, const float* z, const float* u, mdx_rng_t rng, int64_t batch,
+                                int number_of_atoms, int spatial_dimension, float* x_inout, int64_t* a_inout, mdx_stream_t stream)
+{
+    if (!sched_host || batch < 0 || number_of_environments < 0 || capacity < 0 || number_of_atoms < 1) return MDX_ERR_INVALID_ARG;
+    if (spatial_dimension < 1 || spatial_dimension > 3 || capacity > number_of_atoms) return MDX_ERR_INVALID_ARG;
+    if (!d_index && (index_i < 0 || index_i > sched_host->total_time_steps)) return MDX_ERR_INVALID_ARG;
+    if (sched_host->num_classes > MDX_MAX_CLASSES) return MDX_ERR_UNSUPPORTED;
+    if (batch == 0 || capacity == 0 || number_of_environments == 0) return MDX_OK;
+    if (!constrained_x || !constrained_a || !constrained_indices || !counts || !sample_environment || !x_inout || !a_inout)
+        return MDX_ERR_INVALID_ARG;
+    RepaintArgs a{};
+    a.sched = to_dev(sched_host);
+    a.index_i = index_i; a.d_index = d_index;
+    a.cx = constrained_x; a.ca = constrained_a; a.cidx = constrained_indices; a.K = capacity;
+    a.z = z; a.u = u; a.rng = rng;
+    a.B = batch; a.N = number_of_atoms; a.d = spatial_dimension; a.C = sched_host->num_classes;
+    a.x = x_inout; a.a = a_inout;
+    hipLaunchKernelGGL(repaint_rows_per_sample_kernel, dim3(flat_grid(batch * capacity)), dim3(kBlock), 0, as_stream(stream), a,
+                       sample_environment, counts, number_of_environments);
     return launch_status();
 }
 

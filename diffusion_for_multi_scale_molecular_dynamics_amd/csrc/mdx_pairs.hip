@@ -9,6 +9,9 @@
 //   offsets_scan_kernel        exclusive scan of the per-row edge counts (one workgroup) + the edge total
 //   egnn_graph_mask_kernel     EGNN graph, pass 1: one workgroup per structure, per-row neighbour bit masks and counts
 //   egnn_graph_emit_kernel     pass 2: offsets from the counts and the sorted edge list from the masks
+//   excise_environments_kernel the active-learning excisors: one workgroup per central atom, binary64 image distances in LDS,
+//                              slots by counting rank (distance, atom index), centring and embedding in the new box
+//   edit_keep_mask_kernel      the sample edit: which generated atoms lie outside the radius around the active atom
 // 64-wide wavefronts are assumed throughout (gfx950).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -561,6 +564,161 @@ static void launch_graph_two_pass(const float* relative_coordinates, const float
                        edges_out, capacity, status);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Environment excision and the sample edit (active_learning_loop/excisor/*.py, utils.py:98-135,
+// sample_maker/base_sample_maker.py:221-299, excise_and_repaint_sample_maker.py:204-242): binary64, the reference's order
+// ---------------------------------------------------------------------------------------------------------------
+// get_distances_from_reference_point (utils.py:113-135) for one atom: Cartesian difference, per dimension the least of the three
+// squared image differences, the sum in dimension order, the square root
+__device__ __forceinline__ double image_distance(const double* cart, const double* reference_cart, const double* side, int d)
+{
+    double sum = 0.0;
+    for (int a = 0; a < d; ++a) {
+        const double delta = cart[a] - reference_cart[a];
+        double least = delta * delta;
+        const double below = delta - side[a], above = delta + side[a];
+        least = fmin(least, below * below);
+        least = fmin(least, above * above);
+        sum = a == 0 ? least : sum + least;
+    }
+    return sqrt(sum);
+}
+
+struct ExciseArgs {
+    const double *x, *side, *new_side;
+    const int64_t* central;
+    int N, d, mode, neighbours, center, capacity;
+    double radius;
+    int64_t* source;
+    float* constrained_x;
+    int32_t* counts;
+    uint32_t* status;
+};
+
+// One workgroup per central atom.  LDS: the N distances (binary64) and the source atom of every output slot.  An atom's slot
+// is its rank by (distance, atom index), found by counting -- no sort; in radius mode every atom closer than a member is a
+// member, so the rank among all atoms is the rank among the members.
+__global__ __launch_bounds__(kBlock) void excise_environments_kernel(ExciseArgs p)
+{
+    extern __shared__ double excise_lds[];
+    double* dist = excise_lds;
+    int* slot_source = reinterpret_cast<int*>(excise_lds + p.N);
+    __shared__ int members;
+    __shared__ uint32_t bits;
+    const int e = blockIdx.x, N = p.N, d = p.d, cap = p.capacity;
+    const int64_t c = p.central[e];
+    int64_t* source = p.source + (int64_t)e * cap;
+    float* out = p.constrained_x + (int64_t)e * cap * d;
+    if (c < 0 || c >= N) {                                   // (the whole workgroup takes this branch: c is uniform)
+        for (int s = threadIdx.x; s < cap; s += blockDim.x) {
+            source[s] = 0;
+            for (int a = 0; a < d; ++a) out[s * d + a] = 0.0f;
+        }
+        if (threadIdx.x == 0) {
+            p.counts[e] = 0;
+            if (p.status) atomicOr(p.status, MDX_STATUS_EXCISE_CENTRAL_INDEX);
+        }
+        return;
+    }
+    if (threadIdx.x == 0) { members = 0; bits = 0u; }
+    for (int s = threadIdx.x; s < cap; s += blockDim.x) slot_source[s] = -1;     // (stays -1 only where NaN distances share a rank)
+    double side[3], reference[3];
+    for (int a = 0; a < d; ++a) {
+        side[a] = p.side[a];
+        reference[a] = p.x[c * d + a] * side[a];
+    }
+    for (int j = threadIdx.x; j < N; j += blockDim.x) {
+        double cart[3];
+        for (int a = 0; a < d; ++a) cart[a] = p.x[(int64_t)j * d + a] * side[a];
+        dist[j] = image_distance(cart, reference, side, d);
+    }
+    __syncthreads();
+    const int wanted = p.neighbours < N - 1 ? p.neighbours + 1 : N;         // nearest-neighbours mode: the centre and k more
+    for (int j = threadIdx.x; j < N; j += blockDim.x) {
+        const double dj = dist[j];
+        if (p.mode == MDX_EXCISE_RADIUS && !(dj < p.radius)) continue;
+        int rank = 0;
+        for (int i = 0; i < N; ++i) {
+            const double di = dist[i];
+            rank += (di < dj || (di == dj && i < j)) ? 1 : 0;
+        }
+        if (p.mode == MDX_EXCISE_NEIGHBOURS && rank >= wanted) continue;
+        atomicAdd(&members, 1);
+        if (rank < cap) slot_source[rank] = j;
+    }
+    __syncthreads();
+    const int count = members, kept = count < cap ? count : cap;
+    for (int s = threadIdx.x; s < cap; s += blockDim.x) {
+        if (s >= kept) {
+            source[s] = 0;
+            for (int a = 0; a < d; ++a) out[s * d + a] = 0.0f;
+            continue;
+        }
+        const int j = slot_source[s];
+        const int first = slot_source[0];                    // center_structure (base_excisor.py:65-70) centres slot 0
+        if (j < 0 || first < 0) {
+            source[s] = 0;
+            for (int a = 0; a < d; ++a) out[s * d + a] = 0.0f;
+            continue;
+        }
+        source[s] = j;
+        bool outside = false;
+        for (int a = 0; a < d; ++a) {
+            double v = p.x[(int64_t)j * d + a];
+            if (p.center) {
+                v = v + (0.5 - p.x[(int64_t)first * d + a]);
+                double r = fmod(v, 1.0);                     // numpy's mod: the sign of the divisor
+                if (r != 0.0) { if (r < 0.0) r += 1.0; } else { r = 0.0; }
+                v = r;
+            }
+            if (p.new_side) {                                // embed_structure_in_new_box (base_sample_maker.py:250-291)
+                const double cart = (v - 0.5) * side[a] + 0.5 * p.new_side[a];
+                if (!(cart < p.new_side[a] && cart > 0.0)) outside = true;
+                v = cart * (1.0 / p.new_side[a]);            // the reference multiplies by the inverse cell
+            }
+            out[s * d + a] = (float)v;
+        }
+        if (outside) atomicOr(&bits, MDX_STATUS_EXCISE_OUTSIDE_BOX);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        p.counts[e] = count;
+        uint32_t word = bits;
+        if (count > cap) word |= MDX_STATUS_EXCISE_CAPACITY;
+        if (p.status && word) atomicOr(p.status, word);
+    }
+}
+
+struct EditMaskArgs {
+    const float *x, *lattice;
+    int lattice_stride;
+    const int32_t *environment, *active, *counts;
+    int64_t B;
+    int N, d, E;
+    double radius;
+    uint8_t* keep;
+};
+
+__global__ __launch_bounds__(kBlock) void edit_keep_mask_kernel(EditMaskArgs p)
+{
+    const int64_t total = p.B * p.N;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = t / p.N;
+        const int n = (int)(t - b * p.N);
+        const int e = p.environment[b];
+        const int active = e >= 0 && e < p.E ? p.active[e] : -1;
+        if (active < 0 || active >= p.N || n < p.counts[e]) { p.keep[t] = 1; continue; }     // (no environment: nothing is edited)
+        const float* row = p.x + b * p.N * p.d;
+        double side[3], cart[3], reference[3];
+        for (int a = 0; a < p.d; ++a) {
+            side[a] = (double)p.lattice[b * p.lattice_stride + a];
+            cart[a] = (double)row[n * p.d + a] * side[a];
+            reference[a] = (double)row[active * p.d + a] * side[a];
+        }
+        p.keep[t] = image_distance(cart, reference, side, p.d) > p.radius ? 1 : 0;
+    }
+}
+
 }  // namespace
 
 // =================================================================================================================
@@ -673,6 +831,46 @@ int mdx_radius_graph_fill(const float* cart, const float* cell, float rc, int64_
 {
     return mdx_radius_graph_fill_capped(cart, cell, rc, batch, N, unique, offsets, INT64_MAX, edges_out, image_out, shifts_out,
                                         nullptr, stream);
+}
+
+int mdx_excise_environments(const double* relative_coordinates, const double* box_sides, int number_of_atoms, int spatial_dimension,
+                            const int64_t* central_atoms, int number_of_environments, int mode, double radial_cutoff,
+                            int number_of_neighbors, int center_atoms, const double* new_box_sides, int capacity,
+                            int64_t* source_indices, float* constrained_x, int32_t* counts, uint32_t* status, mdx_stream_t stream)
+{
+    if (number_of_atoms < 1 || number_of_environments < 0 || capacity < 1) return MDX_ERR_INVALID_ARG;
+    if (spatial_dimension < 1 || spatial_dimension > 3) return MDX_ERR_INVALID_ARG;
+    if (mode != MDX_EXCISE_RADIUS && mode != MDX_EXCISE_NEIGHBOURS) return MDX_ERR_INVALID_ARG;
+    if (mode == MDX_EXCISE_RADIUS ? !(radial_cutoff > 0.0) : number_of_neighbors < 1) return MDX_ERR_INVALID_ARG;
+    if (number_of_atoms > MDX_EXCISE_MAX_ATOMS || capacity > MDX_EXCISE_MAX_ATOMS) return MDX_ERR_UNSUPPORTED;   // LDS: distances, slots
+    if (number_of_environments == 0) return MDX_OK;
+    if (!relative_coordinates || !box_sides || !central_atoms || !source_indices || !constrained_x || !counts)
+        return MDX_ERR_INVALID_ARG;
+    ExciseArgs a{};
+    a.x = relative_coordinates; a.side = box_sides; a.new_side = new_box_sides; a.central = central_atoms;
+    a.N = number_of_atoms; a.d = spatial_dimension; a.mode = mode; a.neighbours = number_of_neighbors;
+    a.center = center_atoms ? 1 : 0; a.capacity = capacity; a.radius = radial_cutoff;
+    a.source = source_indices; a.constrained_x = constrained_x; a.counts = counts; a.status = status;
+    const size_t lds = sizeof(double) * (size_t)number_of_atoms + sizeof(int) * (size_t)capacity;
+    hipLaunchKernelGGL(excise_environments_kernel, dim3((unsigned)number_of_environments), dim3(kBlock), lds, as_stream(stream), a);
+    return launch_status();
+}
+
+int mdx_edit_keep_mask(const float* relative_coordinates, const float* lattice_parameters, int lattice_stride,
+                       const int32_t* sample_environment, const int32_t* active_atoms, const int32_t* counts,
+                       int number_of_environments, double radius, int64_t batch, int number_of_atoms, int spatial_dimension, uint8_t* keep, mdx_stream_t stream)
+{
+    if (batch < 0 || number_of_atoms < 1 || spatial_dimension < 1 || spatial_dimension > 3) return MDX_ERR_INVALID_ARG;
+    if (lattice_stride < spatial_dimension || !(radius >= 0.0) || number_of_environments < 0) return MDX_ERR_INVALID_ARG;
+    if (batch == 0) return MDX_OK;
+    if (!relative_coordinates || !lattice_parameters || !sample_environment || !active_atoms || !counts || !keep)
+        return MDX_ERR_INVALID_ARG;
+    EditMaskArgs a{};
+    a.x = relative_coordinates; a.lattice = lattice_parameters; a.lattice_stride = lattice_stride;
+    a.environment = sample_environment; a.active = active_atoms; a.counts = counts;
+    a.B = batch; a.N = number_of_atoms; a.d = spatial_dimension; a.E = number_of_environments; a.radius = radius; a.keep = keep;
+    hipLaunchKernelGGL(edit_keep_mask_kernel, dim3(flat_grid(batch * number_of_atoms)), dim3(kBlock), 0, as_stream(stream), a);
+    return launch_status();
 }
 
 }  // extern "C"

@@ -6,7 +6,9 @@ ReferenceOrderNoise  parity mode: every draw is made with torch's CPU default ge
                      torch.manual_seed this reproduces the reference CPU generator's trajectory.
 DevicePhiloxNoise    throughput mode: nothing is drawn on the host; kernels evaluate the counter-based
                      Philox4x32-10 specification of DESIGN.md in registers.
-Both expose `device_rng`; generators pass NULL noise pointers to the kernels when it is True.
+PerEnvironmentNoise  parity mode of a batch that holds several environments (PerSampleConstrainedLangevinGenerator): one host
+                     generator per environment, every draw the concatenation of the environments' own draws.
+All expose `device_rng`; generators pass NULL noise pointers to the kernels when it is True.
 """
 import torch
 
@@ -60,6 +62,31 @@ class ReferenceOrderNoise:
 
     def initial_lattice(self, b, nl, device):
         return self.randn(b, nl).to(device)
+
+
+class PerEnvironmentNoise(ReferenceOrderNoise):
+    """Reference-order draws for a batch of E x S samples in which environment e has a host generator OF ITS OWN, seeded
+    seeds[e]: a draw of shape [E S, ...] is the concatenation over e of a draw [S, ...] from generator e.  Draw for draw this is
+    what the reference's sample maker produces when torch.manual_seed(seeds[e]) precedes environment e
+    (torch.Generator().manual_seed(s) reproduces the default generator after torch.manual_seed(s)), and it does not depend on
+    which environments share a batch."""
+
+    def __init__(self, seeds, samples_per_environment: int):
+        self.generators = [torch.Generator().manual_seed(int(seed)) for seed in seeds]
+        self.samples_per_environment = int(samples_per_environment)
+
+    def _draw(self, draw, shape):
+        shape = tuple(shape[0]) if len(shape) == 1 and not isinstance(shape[0], int) else tuple(shape)
+        S = self.samples_per_environment
+        assert shape[0] == S * len(self.generators), f"a draw of {shape[0]} rows for {len(self.generators)} environments x {S}"
+        with one_host_thread():
+            return torch.cat([draw(S, *shape[1:], generator=g) for g in self.generators])
+
+    def rand(self, *shape) -> torch.Tensor:
+        return self._draw(torch.rand, shape)
+
+    def randn(self, *shape) -> torch.Tensor:
+        return self._draw(torch.randn, shape)
 
 
 class DevicePhiloxNoise:

@@ -281,6 +281,94 @@ def forward_diffusion_step(sched: DeviceSchedule, index_i: int, d_index, z, u, r
     check(rc, "mdx_forward_diffusion_step")
 
 
+def repaint_rows_per_sample(sched: DeviceSchedule, index_i: int, d_index, constrained_x, constrained_a, constrained_indices,
+                            counts, sample_environment, z, u, rng: Rng, x_inout, a_inout):
+    """mdx_repaint_constrained_rows with one constraint table per environment (mdx_repaint_rows_per_sample): tables
+    constrained_x f32 [E,K,d], constrained_a / constrained_indices int64 [E,K], counts int32 [E]; sample b of the batch takes
+    the first counts[e] rows of environment e = sample_environment[b] (int32 [B]).  In place on x_inout [B,N,d], a_inout [B,N]."""
+    B, N, d = x_inout.shape
+    E, K = constrained_a.shape
+    assert constrained_x.shape == (E, K, d) and constrained_indices.shape == (E, K) and counts.shape == (E,)
+    assert sample_environment.shape == (B,) and a_inout.shape == (B, N)
+    rc = lib().mdx_repaint_rows_per_sample(
+        C.byref(sched.c_struct), int(index_i), ptr(d_index, I32, "d_index"), ptr(constrained_x, F32, "constrained_x"),
+        ptr(constrained_a, I64, "constrained_a"), ptr(constrained_indices, I64, "constrained_indices"),
+        ptr(counts, I32, "counts"), E, K, ptr(sample_environment, I32, "sample_environment"), ptr(z, F32, "z"),
+        ptr(u, F32, "u"), rng, B, N, d, ptr(x_inout, F32, "x"), ptr(a_inout, I64, "a"), stream_handle())
+    check(rc, "mdx_repaint_rows_per_sample")
+
+
+class ExcisionCapacityError(_hip.MdxError):
+    """MDX_STATUS_EXCISE_CAPACITY: an environment holds more atoms than the call's capacity; call again with a larger one."""
+
+
+EXCISION_OUTSIDE_BOX = "Excised atoms are outside the new box. Use a larger box or smaller cutoff size for the excision."
+
+
+def excise_environments(relative_coordinates, box_sides, central_atoms, radial_cutoff: Optional[float] = None,
+                        number_of_neighbors: Optional[int] = None, center_atoms: bool = True, new_box_sides=None,
+                        capacity: Optional[int] = None, status: Optional[torch.Tensor] = None):
+    """The environments around `central_atoms` (int64 [E]) of ONE structure, in one launch (mdx_excise_environments): every atom
+    within `radial_cutoff` of the central atom, or its `number_of_neighbors` nearest atoms and itself, ordered by (periodic
+    distance, atom index) -- ties go to the lower index -- optionally translated so that slot 0 sits at the box centre and
+    embedded in the orthogonal box `new_box_sides`.  relative_coordinates f64 [N,d] and box_sides f64 [d] on the device
+    (float32 inputs are widened by the caller: the arithmetic is binary64 in the reference's operation order); N <= 4096, d <= 3.
+
+    Returns (source_indices int64 [E,capacity], constrained_x f32 [E,capacity,d], counts int32 [E]), zero-padded; `capacity`
+    defaults to N.  Without `status` the status word is read once after the call: a count above the capacity raises
+    ExcisionCapacityError, an embedded atom outside the new box the reference's AssertionError, a central index outside
+    [0, N) an IndexError.  With a caller's `status` (int32 [1]) nothing is read on the host."""
+    for name, t in (("relative_coordinates", relative_coordinates), ("box_sides", box_sides), ("central_atoms", central_atoms)):
+        if not t.is_cuda:
+            raise _hip.MdxError(f"{name} lives on {t.device}: the excision kernel runs on the GPU only (no CPU fallback)")
+    N, d = relative_coordinates.shape
+    if d > 3 or N > _hip.EXCISE_MAX_ATOMS:
+        raise _hip.MdxError(f"excision: at most 3 spatial dimensions and {_hip.EXCISE_MAX_ATOMS} atoms, got d = {d}, N = {N}")
+    assert box_sides.shape == (d,) and central_atoms.dim() == 1
+    assert (radial_cutoff is None) != (number_of_neighbors is None), "give a radial cutoff or a number of neighbours"
+    E = central_atoms.shape[0]
+    cap = N if capacity is None else int(capacity)
+    dev = relative_coordinates.device
+    source = torch.empty(E, cap, dtype=I64, device=dev)
+    cx = torch.empty(E, cap, d, dtype=F32, device=dev)
+    counts = torch.empty(E, dtype=I32, device=dev)
+    own = status is None
+    if own:
+        status = torch.zeros(1, dtype=I32, device=dev)
+    mode = _hip.EXCISE_RADIUS if number_of_neighbors is None else _hip.EXCISE_NEIGHBOURS
+    check(lib().mdx_excise_environments(
+        ptr(relative_coordinates, F64, "relative_coordinates"), ptr(box_sides, F64, "box_sides"), N, d,
+        ptr(central_atoms, I64, "central_atoms"), E, mode, float(radial_cutoff or 0.0), int(number_of_neighbors or 0),
+        int(bool(center_atoms)), ptr(new_box_sides, F64, "new_box_sides"), cap, ptr(source, I64, "source_indices"),
+        ptr(cx, F32, "constrained_x"), ptr(counts, I32, "counts"), ptr(status, I32, "status"), stream_handle()),
+        "mdx_excise_environments")
+    if own:
+        word = int(status.item())
+        if word & _hip.STATUS_EXCISE_CENTRAL_INDEX:
+            raise IndexError(f"a central atom index is outside [0, {N})")
+        if word & _hip.STATUS_EXCISE_CAPACITY:
+            raise ExcisionCapacityError(f"an environment holds {int(counts.max())} atoms, more than the capacity {cap}")
+        if word & _hip.STATUS_EXCISE_OUTSIDE_BOX:
+            raise AssertionError(EXCISION_OUTSIDE_BOX)
+    return source, cx, counts
+
+
+def edit_keep_mask(relative_coordinates, lattice_parameters, sample_environment, active_atoms, counts, radius: float):
+    """keep uint8 [B,N] of the excise-and-repaint sample edit (mdx_edit_keep_mask): atom n of sample b stays when it is one of
+    the first counts[e] (constrained) atoms or lies further than `radius` from atom active_atoms[e], e = sample_environment[b]
+    (all three int32), in the sample's own box lattice_parameters[b, :d]; binary64 distances on the widened float32 inputs."""
+    B, N, d = relative_coordinates.shape
+    assert lattice_parameters.dim() == 2 and lattice_parameters.shape[0] == B and lattice_parameters.shape[1] >= d
+    assert sample_environment.shape == (B,) and active_atoms.shape == counts.shape and active_atoms.dim() == 1
+    keep = torch.empty(B, N, dtype=torch.uint8, device=relative_coordinates.device)
+    check(lib().mdx_edit_keep_mask(ptr(relative_coordinates, F32, "relative_coordinates"),
+                                   ptr(lattice_parameters, F32, "lattice_parameters"), lattice_parameters.shape[1],
+                                   ptr(sample_environment, I32, "sample_environment"), ptr(active_atoms, I32, "active_atoms"),
+                                   ptr(counts, I32, "counts"), counts.shape[0], float(radius), B, N, d, ptr(keep, torch.uint8, "keep"),
+                                   stream_handle()), "mdx_edit_keep_mask")
+    return keep
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # N1
 # ----------------------------------------------------------------------------------------------------------------

@@ -55,6 +55,13 @@ extern "C" {
 #define MDX_STATUS_ANALYTICAL_COORDINATES 256u /* the same functions: a relative coordinate outside [0, 1) or not finite
                                             (score/wrapped_gaussian_score.py:156-159 assert); results NaN likewise      */
 
+#define MDX_STATUS_EXCISE_CAPACITY 512u  /* mdx_excise_environments: an environment holds more atoms than the caller's capacity
+                                            (its count is the true one; the first `capacity` slots are written)        */
+#define MDX_STATUS_EXCISE_OUTSIDE_BOX 1024u /* the same function: an embedded atom lies outside (0, L_new)
+                                            (active_learning_loop/sample_maker/base_sample_maker.py:278-283 assert)    */
+#define MDX_STATUS_EXCISE_CENTRAL_INDEX 2048u /* the same function: a central atom index outside [0, number_of_atoms);
+                                            that environment comes out empty                                           */
+
 #define MDX_MAX_CLASSES 8      /* C supported by the fused atom-type kernels */
 #define MDX_PREDICTOR 0
 #define MDX_CORRECTOR 1
@@ -257,6 +264,54 @@ MDX_API int mdx_repaint_constrained_rows(const mdx_schedule_t* sched_host, int i
                                  const int64_t* constrained_indices, int number_of_constraints, const float* z,
                                  const float* u, mdx_rng_t rng, int64_t batch, int number_of_atoms,
                                  int spatial_dimension, float* x_inout, int64_t* a_inout, mdx_stream_t stream);
+
+/* R1 with one constraint table per ENVIRONMENT of the batch (no reference counterpart: the reference's excise-and-repaint
+ * sample maker, active_learning_loop/sample_maker/excise_and_repaint_sample_maker.py:162-174, builds one generator per
+ * environment and runs them one after another).  Sample b belongs to environment e = sample_environment[b] (int32 [B]) and
+ * takes rows 0 .. counts[e]-1 of constrained_x [E,K,d], constrained_a [E,K] and constrained_indices [E,K], K = capacity;
+ * the rows past counts[e] are padding and are skipped, as is a row whose index lies outside [0, N) or whose atom type lies
+ * outside [0, C).  Arithmetic, noise arguments and the Philox counter (item = b N + row, the same tags and draw ids) are those
+ * of mdx_repaint_constrained_rows: with equal environments the two entries write the same bits.  The tables are read at
+ * execution time: a captured launch sees what they hold when the graph is replayed. */
+MDX_API int mdx_repaint_rows_per_sample(const mdx_schedule_t* sched_host, int index_i, const int32_t* d_index,
+                                        const float* constrained_x, const int64_t* constrained_a,
+                                        const int64_t* constrained_indices, const int32_t* counts,
+                                        int number_of_environments, int capacity, const int32_t* sample_environment,
+                                        const float* z, const float* u, mdx_rng_t rng, int64_t batch, int number_of_atoms,
+                                        int spatial_dimension, float* x_inout, int64_t* a_inout, mdx_stream_t stream);
+
+/* Environment excision -- SphericalExcision / NearestNeighborsExcision._excise_one_environment
+ * (active_learning_loop/excisor/spherical_excisor.py:45-68, nearest_neighbors_excisor.py:48-67), center_structure
+ * (excisor/base_excisor.py:65-74) and embed_structure_in_new_box (sample_maker/base_sample_maker.py:247-291) for every
+ * central atom in ONE launch, one workgroup per central atom.  relative_coordinates [N,d] and box_sides [d] are binary64 (an
+ * orthogonal box, like the reference); everything is computed in binary64 in the reference's order:
+ *   distance   (x_j L - x_c L), per dimension min(D^2, (D - L)^2, (D + L)^2), sqrt of the sum   (utils.py:113-135)
+ *   members    mode MDX_EXCISE_RADIUS: distance < radial_cutoff; MDX_EXCISE_NEIGHBOURS: the number_of_neighbors + 1 nearest
+ *   slot       the rank by (distance, atom index): ties go to the LOWER atom index (numpy's argsort leaves them unspecified)
+ *   centring   center_atoms != 0: mod(x + (0.5 - x_slot0), 1), numpy's mod
+ *   embedding  new_box_sides != NULL: ((x - 0.5) L + 0.5 L_new) (1 / L_new); outside (0, L_new): MDX_STATUS_EXCISE_OUTSIDE_BOX
+ * Outputs, zero-padded to `capacity` slots per environment: source_indices int64 [E,capacity], constrained_x float32
+ * [E,capacity,d] (ONE rounding of the binary64 value, as torch.FloatTensor(...) in excise_and_repaint_sample_maker.py:105),
+ * counts int32 [E] (the true member count, also when it exceeds capacity: MDX_STATUS_EXCISE_CAPACITY).  `status` nullable.
+ * number_of_atoms and capacity <= MDX_EXCISE_MAX_ATOMS (MDX_ERR_UNSUPPORTED above); d <= 3. */
+#define MDX_EXCISE_RADIUS 0
+#define MDX_EXCISE_NEIGHBOURS 1
+#define MDX_EXCISE_MAX_ATOMS 4096
+MDX_API int mdx_excise_environments(const double* relative_coordinates, const double* box_sides, int number_of_atoms,
+                                    int spatial_dimension, const int64_t* central_atoms, int number_of_environments, int mode,
+                                    double radial_cutoff, int number_of_neighbors, int center_atoms, const double* new_box_sides,
+                                    int capacity, int64_t* source_indices, float* constrained_x, int32_t* counts,
+                                    uint32_t* status, mdx_stream_t stream);
+
+/* The sample edit -- ExciseAndRepaintSampleMaker.edit_generated_structure (excise_and_repaint_sample_maker.py:224-236) for a
+ * batch: keep[b,n] = n < counts[e] or distance(atom n, atom active_atoms[e]) > radius, e = sample_environment[b], with the
+ * distance of mdx_excise_environments in binary64 on the widened float32 relative_coordinates [B,N,d] and the sample's own box
+ * lattice_parameters[b, :d] (row stride lattice_stride).  active_atoms and counts int32 [number_of_environments]; a sample whose
+ * environment or active atom is out of range keeps every atom.  keep uint8 [B,N]; the caller compacts the ragged result. */
+MDX_API int mdx_edit_keep_mask(const float* relative_coordinates, const float* lattice_parameters, int lattice_stride,
+                               const int32_t* sample_environment, const int32_t* active_atoms, const int32_t* counts,
+                               int number_of_environments, double radius, int64_t batch, int number_of_atoms, int spatial_dimension, uint8_t* keep,
+                               mdx_stream_t stream);
 
 /* RePaint resampling ("2000 steps with resampling", BASELINE configs[4]) -- no reference counterpart: the reference's
  * ConstrainedLangevinGenerator (generators/constrained_langevin_generator.py:94-163) has no resampling loop, so this
