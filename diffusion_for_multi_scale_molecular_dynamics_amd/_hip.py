@@ -21,11 +21,14 @@ STATUS_SW_NEIGHBOURS, STATUS_SW_ATOM_TYPE = 32, 64     # mdx_stillinger_weber_en
 STATUS_ANALYTICAL_SIGMA, STATUS_ANALYTICAL_COORDINATES = 128, 256     # mdx_analytical_score, the wrapped-Gaussian functions
 STATUS_EXCISE_CAPACITY, STATUS_EXCISE_OUTSIDE_BOX, STATUS_EXCISE_CENTRAL_INDEX = 512, 1024, 2048     # mdx_excise_environments
 EXCISE_RADIUS, EXCISE_NEIGHBOURS, EXCISE_MAX_ATOMS = 0, 1, 4096
+STATUS_RANDOM_FILL_COUNT, STATUS_RANDOM_FILL_ENVIRONMENT = 4096, 8192     # mdx_random_fill_environments
+RANDOM_FILL_MAX_ATOMS, RANDOM_FILL_MAX_VOXELS = 1024, 4096
 EGNN_COORD_NORMALIZE, EGNN_COORD_TANH = 1, 2      # MDX_EGNN_COORD_* (coord_flags of mdx_egnn_node_gather / _coord_aggregate)
 EGNN_CHAIN_MAX_LAYERS = 16
 MAX_CLASSES = 8
 TAG_COORD, TAG_GUMBEL, TAG_LATTICE, TAG_INIT, TAG_REPAINT_X0, TAG_BINARY, TAG_REPAINT_Z, TAG_REPAINT_U, \
     TAG_INIT_LATTICE, TAG_RESAMPLE_Z, TAG_RESAMPLE_U = range(11)
+TAG_FILL_UNIFORM, TAG_FILL_TYPE, TAG_FILL_VOXEL = 11, 12, 13
 
 ABI_VERSION = 14         # MDX_ABI_VERSION of include/mdx_hip.h
 ABI_SYMBOLS = (
@@ -44,6 +47,7 @@ ABI_SYMBOLS = (
     "mdx_stillinger_weber_workspace_doubles", "mdx_stillinger_weber_energy_forces",
     "mdx_wrapped_gaussian_sigma_normalized_score", "mdx_log_wrapped_gaussians", "mdx_analytical_score",
     "mdx_repaint_rows_per_sample", "mdx_excise_environments", "mdx_edit_keep_mask",
+    "mdx_random_fill_proposals", "mdx_random_fill_environments",
 )
 MLP_MAX_HIDDEN = 8
 # options of mdx_mlp_pc_sample (include/mdx_hip.h)
@@ -184,6 +188,11 @@ def _declare(L):
     L.mdx_excise_environments.argtypes = [vp, vp, i32, i32, vp, i32, i32, f64, i32, i32, vp, i32, vp, vp, vp, vp, vp]
     L.mdx_edit_keep_mask.restype = i32
     L.mdx_edit_keep_mask.argtypes = [vp, vp, i32, vp, vp, vp, i32, f64, i64, i32, i32, vp, vp]
+    L.mdx_random_fill_proposals.restype = i32
+    L.mdx_random_fill_proposals.argtypes = [u64, u32, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.mdx_random_fill_environments.restype = i32
+    L.mdx_random_fill_environments.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), vp, vp, vp, vp, i32, i32, vp, vp, i32, f64, i64,
+                                               i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mdx_forward_diffusion_step.restype = i32
     L.mdx_forward_diffusion_step.argtypes = [C.POINTER(Schedule), i32, vp, vp, vp, Rng, i64, i32, i32, vp, vp, vp]
     L.mdx_radius_graph_count.restype = i32

@@ -1,2 +1,3 @@
-"""The part of the reference's active-learning loop that stands on the repaint generator: atom selectors, environment excisors
-and the excise-and-repaint sample maker (src/.../active_learning_loop/)."""
+"""The sampling side of the reference's active-learning loop: atom selectors, environment excisors and the four sample makers
+(noop, excise_and_noop, excise_and_repaint on the repaint generator, excise_and_random) with their factory
+(src/.../active_learning_loop/)."""

@@ -133,6 +133,44 @@ class BaseExciseSampleMaker(BaseSampleMaker):
             return self.embed_structure_in_new_box(environment, self.arguments.new_box_lattice_parameters)
         return environment          # "noop"
 
+    def _excise_tables(self, structure: AXL, uncertainty_per_atom: np.array):
+        """(centred environments, the same in the new box, central atom indices, the float32 constraint tables
+        of the repaint generator).  Shared by the makers that batch a frame's environments.  With a kernel
+        excisor and a fixed box the tables come from ONE launch and stay on the device; the numpy structures of the
+        information dictionaries are assembled on the host from the atoms the kernel named."""
+        excisor = self.environment_excisor
+        kernel_tables = None
+        if self.sample_box_strategy == "fixed" and excisor._kernel_mode() is not None:
+            central = self.atom_selector.select_central_atoms(uncertainty_per_atom)
+            limit = self.arguments.max_constrained_substructure
+            if limit != _UNLIMITED_CONSTRAINED_STRUCTURE:
+                central = central[:limit]
+            if len(central) == 0:
+                return [], [], [], None
+            kernel_tables = excisor.excise_constraint_tables(structure, central, self.arguments.new_box_lattice_parameters)
+            source, cx, counts, host_counts = kernel_tables
+            environments = excisor.environments_from_source_indices(structure, source.cpu().numpy(), host_counts, True)
+            central_indices = [0] * len(environments)
+        else:
+            environments, central_indices = self._excise(structure, uncertainty_per_atom)
+        in_new_box = [self._in_new_box(environment) for environment in environments]
+        for embedded, central in zip(in_new_box, central_indices):
+            assert central < len(embedded.X), \
+                ("The active atom index is larger than the number of constrained atoms: "
+                 "this should be impossible, something is wrong. Review code!")
+        if kernel_tables is not None:
+            ca = torch.from_numpy(np.asarray(structure.A, dtype=np.int64)).to(source.device)[source]
+            return environments, in_new_box, central_indices, (cx, ca, None, counts)
+        if not environments:
+            return [], [], [], None
+        E, K, d = len(in_new_box), max(len(e.X) for e in in_new_box), in_new_box[0].X.shape[-1]
+        cx, ca = torch.zeros(E, K, d), torch.zeros(E, K, dtype=torch.int64)
+        for e, embedded in enumerate(in_new_box):
+            cx[e, :len(embedded.X)] = torch.FloatTensor(embedded.X)
+            ca[e, :len(embedded.X)] = torch.LongTensor(embedded.A)
+        counts = torch.tensor([len(e.X) for e in in_new_box], dtype=torch.int32)
+        return environments, in_new_box, central_indices, (cx, ca, None, counts)
+
     @staticmethod
     def _with_structures(sample_info: Dict[str, Any], environment: AXL, environment_in_new_box: AXL) -> Dict[str, Any]:
         sample_info.update({AXL_STRUCTURE_IN_ORIGINAL_BOX: environment, AXL_STRUCTURE_IN_NEW_BOX: environment_in_new_box})

@@ -12,12 +12,18 @@
 //   excise_environments_kernel the active-learning excisors: one workgroup per central atom, binary64 image distances in LDS,
 //                              slots by counting rank (distance, atom index), centring and embedding in the new box
 //   edit_keep_mask_kernel      the sample edit: which generated atoms lie outside the radius around the active atom
+//   random_fill_proposals_kernel    the excise-and-random maker's draws: binary64 uniforms, types and voxel occupancies of every
+//                              attempt of every sample, Philox keyed by (seed, call, sample, attempt)
+//   random_fill_environments_kernel one workgroup per sample: nearest-free-site placement of the constrained atoms, the
+//                              structure, its least pair distance, retry until accepted -- all attempts in one launch
 // 64-wide wavefronts are assumed throughout (gfx950).
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 
 #include "../../include/mdx_hip.h"
 #include "mdx_launch.hpp"
+#include "mdx_math.hpp"
 
 using namespace mdx;
 
@@ -570,7 +576,7 @@ static void launch_graph_two_pass(const float* relative_coordinates, const float
 // ---------------------------------------------------------------------------------------------------------------
 // get_distances_from_reference_point (utils.py:113-135) for one atom: Cartesian difference, per dimension the least of the three
 // squared image differences, the sum in dimension order, the square root
-__device__ __forceinline__ double image_distance(const double* cart, const double* reference_cart, const double* side, int d)
+__device__ __forceinline__ double image_distance_squared(const double* cart, const double* reference_cart, const double* side, int d)
 {
     double sum = 0.0;
     for (int a = 0; a < d; ++a) {
@@ -581,7 +587,12 @@ __device__ __forceinline__ double image_distance(const double* cart, const doubl
         least = fmin(least, above * above);
         sum = a == 0 ? least : sum + least;
     }
-    return sqrt(sum);
+    return sum;
+}
+
+__device__ __forceinline__ double image_distance(const double* cart, const double* reference_cart, const double* side, int d)
+{
+    return sqrt(image_distance_squared(cart, reference_cart, side, d));
 }
 
 struct ExciseArgs {
@@ -716,6 +727,213 @@ __global__ __launch_bounds__(kBlock) void edit_keep_mask_kernel(EditMaskArgs p)
             reference[a] = (double)row[active * p.d + a] * side[a];
         }
         p.keep[t] = image_distance(cart, reference, side, p.d) > p.radius ? 1 : 0;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The excise-and-random sample maker (active_learning_loop/sample_maker/excise_and_random_sample_maker.py:169-328)
+// ---------------------------------------------------------------------------------------------------------------
+struct ProposalArgs {
+    uint64_t seed;
+    uint32_t call;
+    int64_t first_sample;
+    int M, N, d, C, V;
+    double* uniforms;
+    int32_t *types, *voxels;
+};
+
+// a multiple of 2^-53 in [0, 1) from two Philox words: 27 high bits and 26 low bits
+__device__ __forceinline__ double u01_binary64(uint32_t w0, uint32_t w1)
+{
+    return (double)(((uint64_t)(w0 >> 5) << 26) | (uint64_t)(w1 >> 6)) * 1.1102230246251565e-16;
+}
+
+// One workgroup per (sample, attempt).  LDS: one key per voxel, for the ranks of the voxels that the atoms of the last, partial
+// round take (select_occupied_voxels, utils.py:203-212).
+__global__ __launch_bounds__(kBlock) void random_fill_proposals_kernel(ProposalArgs p)
+{
+    extern __shared__ uint32_t proposal_keys[];
+    const int64_t bm = blockIdx.x, b = bm / p.M;
+    const uint32_t m = (uint32_t)(bm - b * p.M), sample = (uint32_t)(p.first_sample + b);
+    const uint32_t k0 = (uint32_t)p.seed, k1 = (uint32_t)(p.seed >> 32), call8 = p.call << 8;
+    const int N = p.N, d = p.d, V = p.V;
+    for (int n = threadIdx.x; n < N; n += blockDim.x) {
+        for (int a = 0; a < d; ++a) {
+            const u32x4 r = philox4x32_10((uint32_t)n, call8 | (uint32_t)a, sample, (m << 8) | MDX_TAG_FILL_UNIFORM, k0, k1);
+            p.uniforms[(bm * N + n) * d + a] = u01_binary64(r.v[0], r.v[1]);
+        }
+        const u32x4 r = philox4x32_10((uint32_t)n, call8, sample, (m << 8) | MDX_TAG_FILL_TYPE, k0, k1);
+        p.types[bm * N + n] = (int32_t)__umulhi(r.v[0], (uint32_t)p.C);
+    }
+    if (!p.voxels) return;
+    const int full = (N / V) * V, rest = N - full;
+    for (int n = threadIdx.x; n < full; n += blockDim.x) p.voxels[bm * N + n] = n % V;
+    if (rest == 0) return;                                   // (uniform over the workgroup)
+    for (int v = threadIdx.x; v < V; v += blockDim.x)
+        proposal_keys[v] = philox4x32_10((uint32_t)v, call8, sample, (m << 8) | MDX_TAG_FILL_VOXEL, k0, k1).v[0];
+    __syncthreads();
+    for (int v = threadIdx.x; v < V; v += blockDim.x) {
+        const uint32_t key = proposal_keys[v];
+        int rank = 0;
+        for (int w = 0; w < V; ++w) {
+            const uint32_t other = proposal_keys[w];
+            rank += (other < key || (other == key && w < v)) ? 1 : 0;
+        }
+        if (rank < rest) p.voxels[bm * N + full + rank] = v;      // the ranks are a permutation: every slot is written once
+    }
+}
+
+struct RandomFillArgs {
+    const double *uniforms, *cx, *sides;
+    const int32_t *types, *voxels, *counts, *active, *environment;
+    const int64_t* ca;
+    int E, K, N, d, M, voxel_mode;
+    int partition[3];
+    double threshold;
+    double* x;
+    int64_t* a;
+    int32_t *active_out, *attempts;
+    uint8_t* accepted;
+    double* min_distance;
+    uint32_t* status;
+};
+
+// is the pair (distance, index) `a` ahead of `b`: the smaller distance, the lower index among equal distances
+__device__ __forceinline__ bool nearer(double da, int ia, double db, int ib) { return da < db || (da == db && ia < ib); }
+
+// One workgroup per sample.  LDS: the N proposed sites and the N atoms of the structure (relative coordinates, binary64), the
+// site behind every slot of the structure, one bit per taken site.  Every branch around a barrier is uniform over the
+// workgroup: it depends on the sample's environment, the attempt and the decision thread 0 publishes.
+__global__ __launch_bounds__(kBlock) void random_fill_environments_kernel(RandomFillArgs p)
+{
+    extern __shared__ double fill_lds[];
+    constexpr int kWaves = kBlock / kWave;
+    __shared__ double wave_best[kWaves];
+    __shared__ int wave_index[kWaves];
+    __shared__ double least_distance;
+    __shared__ int decision;
+    const int N = p.N, d = p.d, words = (N + 31) / 32;
+    double* site = fill_lds;
+    double* atom = fill_lds + (size_t)N * d;
+    int* slot_site = reinterpret_cast<int*>(fill_lds + 2 * (size_t)N * d);
+    uint32_t* taken = reinterpret_cast<uint32_t*>(slot_site + N);
+    const int64_t b = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const int e = p.environment[b];
+    const bool known = e >= 0 && e < p.E;
+    const int count = known ? p.counts[e] : 0;
+    const int active = known ? p.active[e] : -1;
+    double* out_x = p.x + b * N * d;
+    int64_t* out_a = p.a + b * N;
+    uint32_t bits = 0u;
+    if (!known) bits = MDX_STATUS_RANDOM_FILL_ENVIRONMENT;
+    else if (count > N || count > p.K) bits = MDX_STATUS_RANDOM_FILL_COUNT;
+    else if (active < 0 || active >= count) bits = MDX_STATUS_RANDOM_FILL_ENVIRONMENT;       // (count < 1 ends here too)
+    if (bits) {
+        for (int s = tid; s < N; s += blockDim.x) {
+            out_a[s] = 0;
+            for (int a = 0; a < d; ++a) out_x[s * d + a] = 0.0;
+        }
+        if (tid == 0) {
+            p.active_out[b] = 0; p.attempts[b] = 0; p.accepted[b] = 0; p.min_distance[b] = 0.0;
+            if (p.status) atomicOr(p.status, bits);
+        }
+        return;
+    }
+    double side[3];
+    for (int a = 0; a < d; ++a) side[a] = p.sides[e * d + a];
+    const double* cx = p.cx + (int64_t)e * p.K * d;
+    const double infinity = __builtin_inf();
+    for (int m = 0; m < p.M; ++m) {
+        const int64_t bm = b * p.M + m;
+        // the sites of this attempt
+        for (int n = tid; n < N; n += blockDim.x) {
+            int v = p.voxel_mode ? p.voxels[bm * N + n] : 0;
+            for (int a = d - 1; a >= 0; --a) {
+                double value = p.uniforms[(bm * N + n) * d + a];
+                if (p.voxel_mode) {
+                    const int parts = p.partition[a], i = v % parts;
+                    v /= parts;
+                    value = (double)i * (1.0 / (double)parts) + value / (double)parts;
+                }
+                site[n * d + a] = value;
+            }
+        }
+        for (int w = tid; w < words; w += blockDim.x) taken[w] = 0u;
+        __syncthreads();
+        // every constrained atom in order takes the nearest site still free
+        for (int k = 0; k < count; ++k) {
+            double reference[3];
+            for (int a = 0; a < d; ++a) reference[a] = cx[k * d + a] * side[a];
+            double best = infinity;
+            int index = INT_MAX;
+            for (int n = tid; n < N; n += blockDim.x) {
+                if ((taken[n >> 5] >> (n & 31)) & 1u) continue;
+                double cart[3];
+                for (int a = 0; a < d; ++a) cart[a] = site[n * d + a] * side[a];
+                const double distance = image_distance(cart, reference, side, d);
+                if (nearer(distance, n, best, index)) { best = distance; index = n; }
+            }
+#pragma unroll
+            for (int o = kWave / 2; o > 0; o >>= 1) {
+                const double other = __shfl_xor(best, o, kWave);
+                const int other_index = __shfl_xor(index, o, kWave);
+                if (nearer(other, other_index, best, index)) { best = other; index = other_index; }
+            }
+            if (lane == 0) { wave_best[wave] = best; wave_index[wave] = index; }
+            __syncthreads();
+            if (tid == 0) {
+                for (int w = 1; w < kWaves; ++w)
+                    if (nearer(wave_best[w], wave_index[w], best, index)) { best = wave_best[w]; index = wave_index[w]; }
+                if (index == INT_MAX)                        // only NaN distances: the lowest free site (count <= N: there is one)
+                    for (index = 0; index < N - 1 && ((taken[index >> 5] >> (index & 31)) & 1u); ++index) {}
+                taken[index >> 5] |= 1u << (index & 31);
+                slot_site[k] = index;
+            }
+            __syncthreads();
+        }
+        // the structure: the constrained atoms, then the free sites in ascending order
+        for (int s = tid; s < count; s += blockDim.x)
+            for (int a = 0; a < d; ++a) atom[s * d + a] = cx[s * d + a];
+        for (int n = tid; n < N; n += blockDim.x) {
+            if ((taken[n >> 5] >> (n & 31)) & 1u) continue;
+            int before = __popc(taken[n >> 5] & ((1u << (n & 31)) - 1u));
+            for (int w = 0; w < (n >> 5); ++w) before += __popc(taken[w]);
+            const int slot = count + n - before;
+            slot_site[slot] = n;
+            for (int a = 0; a < d; ++a) atom[slot * d + a] = site[n * d + a];
+        }
+        __syncthreads();
+        // the least squared distance over the pairs i < j (the distance is symmetric, bit for bit)
+        double least = infinity;
+        for (int pair = tid; pair < N * N; pair += blockDim.x) {
+            const int i = pair / N, j = pair - i * N;
+            if (j <= i) continue;
+            double first[3], second[3];
+            for (int a = 0; a < d; ++a) { first[a] = atom[i * d + a] * side[a]; second[a] = atom[j * d + a] * side[a]; }
+            least = fmin(least, image_distance_squared(second, first, side, d));
+        }
+#pragma unroll
+        for (int o = kWave / 2; o > 0; o >>= 1) least = fmin(least, __shfl_xor(least, o, kWave));
+        if (lane == 0) wave_best[wave] = least;
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < kWaves; ++w) least = fmin(least, wave_best[w]);
+            least_distance = sqrt(least);
+            decision = least_distance > p.threshold ? 1 : 0;
+        }
+        __syncthreads();
+        if (decision || m == p.M - 1) {
+            for (int s = tid; s < N; s += blockDim.x) {
+                for (int a = 0; a < d; ++a) out_x[s * d + a] = atom[s * d + a];
+                out_a[s] = s < count ? p.ca[(int64_t)e * p.K + s] : (int64_t)p.types[bm * N + slot_site[s]];
+            }
+            if (tid == 0) {
+                p.active_out[b] = active; p.attempts[b] = m + 1; p.accepted[b] = (uint8_t)decision;
+                p.min_distance[b] = least_distance;
+            }
+            return;
+        }
     }
 }
 
@@ -870,6 +1088,67 @@ int mdx_edit_keep_mask(const float* relative_coordinates, const float* lattice_p
     a.environment = sample_environment; a.active = active_atoms; a.counts = counts;
     a.B = batch; a.N = number_of_atoms; a.d = spatial_dimension; a.E = number_of_environments; a.radius = radius; a.keep = keep;
     hipLaunchKernelGGL(edit_keep_mask_kernel, dim3(flat_grid(batch * number_of_atoms)), dim3(kBlock), 0, as_stream(stream), a);
+    return launch_status();
+}
+
+int mdx_random_fill_proposals(uint64_t seed, uint32_t call, int64_t first_sample, int64_t batch, int max_attempts,
+                              int number_of_atoms, int spatial_dimension, int num_atom_types, int number_of_voxels, double* uniforms,
+                              int32_t* types, int32_t* voxels, mdx_stream_t stream)
+{
+    if (batch < 0 || first_sample < 0 || max_attempts < 1 || number_of_atoms < 1 || num_atom_types < 1) return MDX_ERR_INVALID_ARG;
+    if (spatial_dimension < 1 || spatial_dimension > 3 || number_of_voxels < 0) return MDX_ERR_INVALID_ARG;
+    if ((number_of_voxels > 0) != (voxels != nullptr)) return MDX_ERR_INVALID_ARG;
+    if (number_of_atoms > MDX_RANDOM_FILL_MAX_ATOMS || number_of_voxels > MDX_RANDOM_FILL_MAX_VOXELS) return MDX_ERR_UNSUPPORTED;
+    if (call >= (1u << 24) || max_attempts >= (1 << 24) || first_sample + batch > 0x100000000LL) return MDX_ERR_UNSUPPORTED;
+    if (batch * max_attempts > 0x7fffffffLL) return MDX_ERR_UNSUPPORTED;                     // one workgroup per (sample, attempt)
+    if (batch == 0) return MDX_OK;
+    if (!uniforms || !types) return MDX_ERR_INVALID_ARG;
+    ProposalArgs a{};
+    a.seed = seed; a.call = call; a.first_sample = first_sample; a.M = max_attempts; a.N = number_of_atoms;
+    a.d = spatial_dimension; a.C = num_atom_types; a.V = number_of_voxels; a.uniforms = uniforms; a.types = types; a.voxels = voxels;
+    hipLaunchKernelGGL(random_fill_proposals_kernel, dim3((unsigned)(batch * max_attempts)), dim3(kBlock),
+                       sizeof(uint32_t) * (size_t)(number_of_voxels > 0 ? number_of_voxels : 1), as_stream(stream), a);
+    return launch_status();
+}
+
+int mdx_random_fill_environments(const double* uniforms, const int32_t* types, const int32_t* voxels, const int32_t* partition,
+                                 const double* constrained_x, const int64_t* constrained_a, const int32_t* counts,
+                                 const int32_t* active, int number_of_environments, int constrained_capacity,
+                                 const int32_t* sample_environment, const double* box_sides, int max_attempts,
+                                 double minimal_interatomic_distance, int64_t batch, int number_of_atoms, int spatial_dimension,
+                                 double* x, int64_t* a_out, int32_t* active_out, int32_t* attempts, uint8_t* accepted,
+                                 double* min_distance, uint32_t* status, mdx_stream_t stream)
+{
+    if (batch < 0 || max_attempts < 1 || number_of_atoms < 2 || number_of_environments < 1 || constrained_capacity < 1)
+        return MDX_ERR_INVALID_ARG;
+    if (spatial_dimension < 1 || spatial_dimension > 3 || (partition != nullptr) != (voxels != nullptr)) return MDX_ERR_INVALID_ARG;
+    if (!(minimal_interatomic_distance == minimal_interatomic_distance)) return MDX_ERR_INVALID_ARG;          // NaN
+    if (number_of_atoms > MDX_RANDOM_FILL_MAX_ATOMS || constrained_capacity > MDX_RANDOM_FILL_MAX_ATOMS) return MDX_ERR_UNSUPPORTED;
+    if (batch > 0x7fffffffLL) return MDX_ERR_UNSUPPORTED;
+    if (batch == 0) return MDX_OK;
+    if (!uniforms || !types || !constrained_x || !constrained_a || !counts || !active || !sample_environment || !box_sides)
+        return MDX_ERR_INVALID_ARG;
+    if (!x || !a_out || !active_out || !attempts || !accepted || !min_distance) return MDX_ERR_INVALID_ARG;
+    RandomFillArgs r{};
+    r.uniforms = uniforms; r.types = types; r.voxels = voxels; r.cx = constrained_x; r.ca = constrained_a; r.counts = counts;
+    r.active = active; r.environment = sample_environment; r.sides = box_sides; r.E = number_of_environments;
+    r.K = constrained_capacity; r.N = number_of_atoms; r.d = spatial_dimension; r.M = max_attempts;
+    r.voxel_mode = partition ? 1 : 0;
+    for (int k = 0; k < 3; ++k) r.partition[k] = 1;
+    if (partition) {
+        int64_t voxels_in_all = 1;
+        for (int k = 0; k < spatial_dimension; ++k) {
+            if (partition[k] < 1) return MDX_ERR_INVALID_ARG;
+            r.partition[k] = partition[k];
+            voxels_in_all *= partition[k];
+            if (voxels_in_all > MDX_RANDOM_FILL_MAX_VOXELS) return MDX_ERR_UNSUPPORTED;
+        }
+    }
+    r.threshold = minimal_interatomic_distance; r.x = x; r.a = a_out; r.active_out = active_out; r.attempts = attempts;
+    r.accepted = accepted; r.min_distance = min_distance; r.status = status;
+    const size_t lds = sizeof(double) * 2 * (size_t)number_of_atoms * spatial_dimension + sizeof(int) * (size_t)number_of_atoms +
+                       sizeof(uint32_t) * (size_t)((number_of_atoms + 31) / 32);              // <= 53 376 B at the limits
+    hipLaunchKernelGGL(random_fill_environments_kernel, dim3((unsigned)batch), dim3(kBlock), lds, as_stream(stream), r);
     return launch_status();
 }
 

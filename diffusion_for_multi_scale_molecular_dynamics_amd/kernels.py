@@ -369,6 +369,79 @@ def edit_keep_mask(relative_coordinates, lattice_parameters, sample_environment,
     return keep
 
 
+RANDOM_FILL_TOO_MANY_CONSTRAINED = "There are more constrained atoms {} than total number of atoms {}."
+
+
+def random_fill_proposals(seed: int, call: int, first_sample: int, batch: int, max_attempts: int, number_of_atoms: int,
+                          spatial_dimension: int, num_atom_types: int, number_of_voxels: int, device):
+    """The device draws of the excise-and-random maker (mdx_random_fill_proposals): uniforms f64 [B,M,N,d] in [0, 1), types
+    int32 [B,M,N] in [0, num_atom_types) and, with number_of_voxels > 0, voxel occupancies int32 [B,M,N] (None otherwise) by
+    the reference's rule: all voxels once per full round, the rest a random subset without replacement.  Philox keyed by
+    (seed, call, first_sample + b, attempt): a sample's numbers do not depend on the batch it is drawn in."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _hip.MdxError(f"the proposals are drawn on the GPU; got device {device} (no CPU fallback)")
+    B, M, N, d = int(batch), int(max_attempts), int(number_of_atoms), int(spatial_dimension)
+    with torch.cuda.device(device):
+        uniforms = torch.empty(B, M, N, d, dtype=F64, device=device)
+        types = torch.empty(B, M, N, dtype=I32, device=device)
+        voxels = torch.empty(B, M, N, dtype=I32, device=device) if number_of_voxels else None
+        check(lib().mdx_random_fill_proposals(int(seed) & 0xFFFFFFFFFFFFFFFF, int(call), int(first_sample), B, M, N, d,
+                                              int(num_atom_types), int(number_of_voxels), ptr(uniforms, F64, "uniforms"),
+                                              ptr(types, I32, "types"), ptr(voxels, I32, "voxels"), stream_handle()),
+              "mdx_random_fill_proposals")
+    return uniforms, types, voxels
+
+
+def random_fill_environments(uniforms, types, voxels, partition, constrained_x, constrained_a, counts, active,
+                             sample_environment, box_sides, minimal_interatomic_distance: float,
+                             status: Optional[torch.Tensor] = None):
+    """Placement, retry and acceptance of the excise-and-random maker for a batch of samples, one workgroup per sample and all
+    attempts in one launch (mdx_random_fill_environments).  Proposals uniforms f64 [B,M,N,d], types int32 [B,M,N], voxels int32
+    [B,M,N] with the voxels per axis `partition` (a sequence of d ints) or both None; constraint tables constrained_x f64
+    [E,K,d], constrained_a int64 [E,K], counts / active int32 [E]; sample_environment int32 [B]; box_sides f64 [E,d].
+
+    Returns (x f64 [B,N,d], a int64 [B,N], active_out int32 [B], attempts int32 [B], accepted uint8 [B], min_distance f64 [B]).
+    Without `status` the status word is read once after the call: more constrained atoms than atoms raises the reference's
+    AssertionError, an environment or active index out of range an IndexError.  With a caller's `status` (int32 [1]) nothing is
+    read on the host."""
+    B, M, N, d = uniforms.shape
+    E, K = constrained_a.shape
+    if d > 3 or N > _hip.RANDOM_FILL_MAX_ATOMS or K > _hip.RANDOM_FILL_MAX_ATOMS:
+        raise _hip.MdxError(f"random fill: at most 3 spatial dimensions and {_hip.RANDOM_FILL_MAX_ATOMS} atoms, "
+                            f"got d = {d}, N = {N}, K = {K}")
+    assert types.shape == (B, M, N) and constrained_x.shape == (E, K, d) and counts.shape == (E,) and active.shape == (E,)
+    assert sample_environment.shape == (B,) and box_sides.shape == (E, d)
+    assert (voxels is None) == (partition is None), "voxel occupancies and the partition go together"
+    words = None
+    if partition is not None:
+        assert voxels.shape == (B, M, N) and len(partition) == d
+        words = (C.c_int32 * d)(*[int(v) for v in partition])
+    dev = uniforms.device
+    x = torch.empty(B, N, d, dtype=F64, device=dev)
+    a = torch.empty(B, N, dtype=I64, device=dev)
+    active_out, attempts = torch.empty(B, dtype=I32, device=dev), torch.empty(B, dtype=I32, device=dev)
+    accepted = torch.empty(B, dtype=torch.uint8, device=dev)
+    min_distance = torch.empty(B, dtype=F64, device=dev)
+    own = status is None
+    if own:
+        status = torch.zeros(1, dtype=I32, device=dev)
+    check(lib().mdx_random_fill_environments(
+        ptr(uniforms, F64, "uniforms"), ptr(types, I32, "types"), ptr(voxels, I32, "voxels"), words,
+        ptr(constrained_x, F64, "constrained_x"), ptr(constrained_a, I64, "constrained_a"), ptr(counts, I32, "counts"),
+        ptr(active, I32, "active"), E, K, ptr(sample_environment, I32, "sample_environment"), ptr(box_sides, F64, "box_sides"),
+        M, float(minimal_interatomic_distance), B, N, d, ptr(x, F64, "x"), ptr(a, I64, "a"), ptr(active_out, I32, "active_out"),
+        ptr(attempts, I32, "attempts"), ptr(accepted, torch.uint8, "accepted"), ptr(min_distance, F64, "min_distance"),
+        ptr(status, I32, "status"), stream_handle()), "mdx_random_fill_environments")
+    if own:
+        word = int(status.item())
+        if word & _hip.STATUS_RANDOM_FILL_COUNT:
+            raise AssertionError(RANDOM_FILL_TOO_MANY_CONSTRAINED.format(int(counts.max()), N))
+        if word & _hip.STATUS_RANDOM_FILL_ENVIRONMENT:
+            raise IndexError(f"a sample's environment is outside [0, {E}) or an active atom is not a constrained atom")
+    return x, a, active_out, attempts, accepted, min_distance
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # N1
 # ----------------------------------------------------------------------------------------------------------------

@@ -61,6 +61,11 @@ extern "C" {
                                             (active_learning_loop/sample_maker/base_sample_maker.py:278-283 assert)    */
 #define MDX_STATUS_EXCISE_CENTRAL_INDEX 2048u /* the same function: a central atom index outside [0, number_of_atoms);
                                             that environment comes out empty                                           */
+#define MDX_STATUS_RANDOM_FILL_COUNT 4096u /* mdx_random_fill_environments: an environment holds more constrained atoms than
+                                            the sample has atoms (active_learning_loop/sample_maker/
+                                            excise_and_random_sample_maker.py:305-308 assert); its samples come out zero     */
+#define MDX_STATUS_RANDOM_FILL_ENVIRONMENT 8192u /* the same function: a sample names an environment outside [0, E), or the
+                                            environment's active atom is not one of its constrained atoms; zero likewise  */
 
 #define MDX_MAX_CLASSES 8      /* C supported by the fused atom-type kernels */
 #define MDX_PREDICTOR 0
@@ -78,6 +83,9 @@ extern "C" {
 #define MDX_TAG_INIT_LATTICE 8
 #define MDX_TAG_RESAMPLE_Z 9
 #define MDX_TAG_RESAMPLE_U 10
+#define MDX_TAG_FILL_UNIFORM 11
+#define MDX_TAG_FILL_TYPE 12
+#define MDX_TAG_FILL_VOXEL 13
 
 #if defined(__GNUC__)
 #define MDX_API __attribute__((visibility("default")))
@@ -312,6 +320,54 @@ MDX_API int mdx_edit_keep_mask(const float* relative_coordinates, const float* l
                                const int32_t* sample_environment, const int32_t* active_atoms, const int32_t* counts,
                                int number_of_environments, double radius, int64_t batch, int number_of_atoms, int spatial_dimension, uint8_t* keep,
                                mdx_stream_t stream);
+
+/* The excise-and-random sample maker (active_learning_loop/sample_maker/excise_and_random_sample_maker.py:169-328) for every
+ * sample of a frame at once.  Two functions: the proposals of all max_attempts attempts, then placement, retry and acceptance.
+ *
+ * mdx_random_fill_proposals -- the device draws.  For sample b < batch and attempt m < max_attempts:
+ *   uniforms f64 [B,M,N,d] in [0, 1), types int32 [B,M,N] in [0, num_atom_types), and, with number_of_voxels > 0, voxels
+ *   int32 [B,M,N] by select_occupied_voxels' rule (active_learning_loop/utils.py:203-212): atom n < (N / V) V takes voxel
+ *   n mod V (all voxels once per full round); the N mod V atoms left take distinct voxels, the one after the other the voxels
+ *   of rank 0, 1, ... by (key, voxel index) of one 32-bit Philox key per voxel: a uniformly random ordered subset.
+ * Philox4x32-10 with key = seed and counter = (item, (call << 8) | sub, first_sample + b, (m << 8) | tag): a sample's numbers
+ * depend on (seed, call, its index, the attempt) and not on the batch it sits in.
+ *   MDX_TAG_FILL_UNIFORM  item = atom, sub = axis: words w0, w1 give ((w0 >> 5) 2^26 + (w1 >> 6)) 2^-53, a multiple of 2^-53
+ *                         in [0, 1) -- 27 high and 26 low bits, every binary64 of that grid equally likely
+ *   MDX_TAG_FILL_TYPE     item = atom, sub = 0: the high word of w0 * num_atom_types (the bias is below num_atom_types 2^-32)
+ *   MDX_TAG_FILL_VOXEL    item = voxel, sub = 0: the key w0
+ * voxels NULL with number_of_voxels = 0.  N <= MDX_RANDOM_FILL_MAX_ATOMS, V <= MDX_RANDOM_FILL_MAX_VOXELS, d <= 3,
+ * call and max_attempts < 2^24, first_sample + batch <= 2^32.
+ *
+ * mdx_random_fill_environments -- one workgroup per sample; nothing is read back between attempts.  Sample b belongs to
+ * environment e = sample_environment[b]: its first counts[e] atoms are the rows of constrained_x f64 [E,K,d] / constrained_a
+ * int64 [E,K], untouched (binary64 copies), in the box box_sides f64 [E,d] (orthogonal).  For attempt m = 0, 1, ... until one
+ * is accepted:
+ *   sites      uniforms[b,m]; with partition != NULL (a HOST pointer to d ints, the voxels per axis; voxel v = (i0 p1 + i1) p2
+ *              + i2) site = i_a (1 / p_a) + u / p_a, in binary64 in that order (numpy's linspace corner, divide, add)
+ *   placement  constrained atom k = 0 .. count-1 in order takes the nearest site not yet taken, by the periodic distance of
+ *              mdx_excise_environments (utils.py:113-135); equal distances go to the LOWER site index
+ *   structure  the constrained atoms in their own order with their own coordinates and types, then the sites not taken in
+ *              ascending site index with types[b,m,site]
+ *   distance   the least periodic distance over all pairs i != j: the least sum of squares, one sqrt
+ *   accepted   distance > minimal_interatomic_distance
+ * The last attempt is returned when none is accepted.  Outputs: x f64 [B,N,d], a int64 [B,N], active_out int32 [B] (=
+ * active[e], the active atom's index in the constrained order), attempts int32 [B] (1-based: the attempt returned), accepted
+ * uint8 [B], min_distance f64 [B].  `status` (nullable): MDX_STATUS_RANDOM_FILL_COUNT / _ENVIRONMENT; such a sample comes
+ * out zero with attempts = 0.  Limits (the workgroup's LDS holds the sites and the structure): 2 <= N <=
+ * MDX_RANDOM_FILL_MAX_ATOMS, K <= MDX_RANDOM_FILL_MAX_ATOMS (MDX_ERR_UNSUPPORTED above), d <= 3, max_attempts >= 1. */
+#define MDX_RANDOM_FILL_MAX_ATOMS 1024
+#define MDX_RANDOM_FILL_MAX_VOXELS 4096
+MDX_API int mdx_random_fill_proposals(uint64_t seed, uint32_t call, int64_t first_sample, int64_t batch, int max_attempts,
+                                      int number_of_atoms, int spatial_dimension, int num_atom_types, int number_of_voxels,
+                                      double* uniforms, int32_t* types, int32_t* voxels, mdx_stream_t stream);
+MDX_API int mdx_random_fill_environments(const double* uniforms, const int32_t* types, const int32_t* voxels,
+                                         const int32_t* partition, const double* constrained_x, const int64_t* constrained_a,
+                                         const int32_t* counts, const int32_t* active, int number_of_environments,
+                                         int constrained_capacity, const int32_t* sample_environment, const double* box_sides,
+                                         int max_attempts, double minimal_interatomic_distance, int64_t batch,
+                                         int number_of_atoms, int spatial_dimension, double* x, int64_t* a, int32_t* active_out,
+                                         int32_t* attempts, uint8_t* accepted, double* min_distance, uint32_t* status,
+                                         mdx_stream_t stream);
 
 /* RePaint resampling ("2000 steps with resampling", BASELINE configs[4]) -- no reference counterpart: the reference's
  * ConstrainedLangevinGenerator (generators/constrained_langevin_generator.py:94-163) has no resampling loop, so this
