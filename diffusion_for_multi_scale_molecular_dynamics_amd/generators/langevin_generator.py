@@ -630,7 +630,7 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
         words = tuple(None if w is None else w.data_ptr() for w in (self._call_word, self._status))   # read by the captured kernels
         net = self.axl_network
         return (tuple(start.X.shape), tuple(start.L.shape), str(start.X.device), hooks.capture_key(net), settings, words,
-                tuple((p.data_ptr(), p._version) for p in net.parameters()))
+                kernels.parameter_stamp(*net.parameters()))
 
     def _sample_with_graph(self, start: AXL, starting_step_index: int, ending_step_index: int) -> AXL:
         """The iteration is captured ONCE per (shape, network state) and kept: later sample() calls copy their starting

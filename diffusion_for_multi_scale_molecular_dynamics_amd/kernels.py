@@ -740,9 +740,10 @@ class MlpPack:
             setattr(m, f"b_out_{name}", bias(layer))
         m.packed_image = None
         m.folded_input = None
-        self.folded = _fold_input_layers(network, m, device)
+        first, _, out = _folded_matrices(network, m)
+        self.folded = _folded_layer(first, device)
         m.folded_output = None
-        self.folded_out = _fold_output_layers(network, device) if self.folded is not None else None
+        self.folded_out = _folded_layer(out, device)
         m.folded_padded = None
         if self.folded is not None and self.folded_out is not None:
             m.folded_input = self.folded.data_ptr()
@@ -762,56 +763,49 @@ class MlpPack:
         self.number_of_atoms, self.num_classes, self.spatial_dimension = m.number_of_atoms, m.num_classes, m.spatial_dimension
 
 
-def _fold_input_layers(network, m, device):
-    """The five embedding layers folded into hidden layer 0 (mdx_mlp_t.folded_input): they are linear and no activation
-    lies between them and the first hidden layer (mlp_score_network.py:299-344).  Products in binary64, rounded once.
-    Input of the folded layer: [cos (N d) | sin (N d) | sigma | t | atom-type embeddings (N e_a) | lattice emb. (e_l)]."""
+def _folded_matrices(network, m):
+    """The network as n_hidden linear maps, in binary64 on the host: ((W_first [H, F], b_first [H]) or None, [(W_k, b_k) of the
+    middle hidden layers], (W_out [outputs, H], b_out) or None).  The ONLY place the folded products are formed, each rounded
+    once by its user, so mdx_mlp_t.folded_input, folded_output and folded_padded hold the same bits.
+    first: the five embedding layers folded into hidden layer 0 -- they are linear and no activation lies between them and the
+    first hidden layer (mlp_score_network.py:299-344); its input is [cos (N d) | sin (N d) | sigma | t | atom-type embeddings
+    (N e_a) | lattice emb. (e_l)].  None when hidden layer 0 does not have that input width (then nothing is folded).
+    out: the last hidden layer (no activation follows it, mlp_score_network.py:337-344) folded into the three output heads,
+    outputs ordered logits | score_x | score_l.  Needs >= 2 hidden layers."""
     f64 = torch.float64
     with torch.no_grad():
         w0 = network.mlp_layers[0].weight.detach().to(f64).cpu()           # [H, ec + en + et + N ea + el]
         b0 = network.mlp_layers[0].bias.detach().to(f64).cpu()
         ec, en, et = m.e_coordinates, m.e_noise, m.e_time
-        na, el = m.number_of_atoms * m.e_atom_type, m.e_lattice
-        if w0.shape[1] != ec + en + et + na + el:
-            return None
-        o1, o2, o3, o4 = ec, ec + en, ec + en + et, ec + en + et + na
-        wc, bc = (t.detach().to(f64).cpu() for t in (network.relative_coordinates_embedding_layer.weight,
-                                                       network.relative_coordinates_embedding_layer.bias))
-        wn, bn = (t.detach().to(f64).cpu() for t in (network.noise_embedding_layer.weight,
-                                                       network.noise_embedding_layer.bias))
-        wt_, bt = (t.detach().to(f64).cpu() for t in (network.time_embedding_layer.weight,
-                                                        network.time_embedding_layer.bias))
-        columns = torch.cat([w0[:, :o1] @ wc,                     # [H, 2 N d]: cos block then sin block, as the module
-                             w0[:, o1:o2] @ wn,                   # [H, 1]  sigma
-                             w0[:, o2:o3] @ wt_,                  # [H, 1]  time
-                             w0[:, o3:o4],                        # [H, N ea]
-                             w0[:, o4:]], dim=1)                  # [H, el]
-        bias = b0 + w0[:, :o1] @ bc + w0[:, o1:o2] @ bn + w0[:, o2:o3] @ bt
-        return torch.cat([_quad_image(columns), bias]).to(device=device, dtype=F32).contiguous()
-
-
-def _folded_matrices(network, m):
-    """(W_first [H, F], b_first [H]), [(W_k, b_k) of the middle hidden layers], (W_out [outputs, H], b_out) in binary64: the
-    network as n_hidden linear maps (see _fold_input_layers / _fold_output_layers)."""
-    f64 = torch.float64
-    with torch.no_grad():
-        w0 = network.mlp_layers[0].weight.detach().to(f64).cpu()
-        b0 = network.mlp_layers[0].bias.detach().to(f64).cpu()
-        ec, en, et = m.e_coordinates, m.e_noise, m.e_time
         na = m.number_of_atoms * m.e_atom_type
         o1, o2, o3, o4 = ec, ec + en, ec + en + et, ec + en + et + na
+        if w0.shape[1] != o4 + m.e_lattice:
+            return None, [], None
         cpu = lambda t: t.detach().to(f64).cpu()       # noqa: E731
         wc, bc = cpu(network.relative_coordinates_embedding_layer.weight), cpu(network.relative_coordinates_embedding_layer.bias)
         wn, bn = cpu(network.noise_embedding_layer.weight), cpu(network.noise_embedding_layer.bias)
         wt_, bt = cpu(network.time_embedding_layer.weight), cpu(network.time_embedding_layer.bias)
-        first = torch.cat([w0[:, :o1] @ wc, w0[:, o1:o2] @ wn, w0[:, o2:o3] @ wt_, w0[:, o3:o4], w0[:, o4:]], dim=1)
+        first = torch.cat([w0[:, :o1] @ wc,                     # [H, 2 N d]: cos block then sin block, as the module
+                           w0[:, o1:o2] @ wn,                   # [H, 1]  sigma
+                           w0[:, o2:o3] @ wt_,                  # [H, 1]  time
+                           w0[:, o3:o4],                        # [H, N ea]
+                           w0[:, o4:]], dim=1)                  # [H, el]
         first_bias = b0 + w0[:, :o1] @ bc + w0[:, o1:o2] @ bn + w0[:, o2:o3] @ bt
+        if len(network.mlp_layers) < 2:
+            return (first, first_bias), [], None
         mids = [(cpu(layer.weight), cpu(layer.bias)) for layer in list(network.mlp_layers)[1:-1]]
         last = network.mlp_layers[-1]
         heads = (network.output_A_layer, network.output_X_layer, network.output_L_layer)
-        w_heads = torch.cat([cpu(h.weight) for h in heads], dim=0)
+        w_heads = torch.cat([cpu(h.weight) for h in heads], dim=0)        # [N C + N d + nl, H]
         b_heads = torch.cat([cpu(h.bias) for h in heads], dim=0)
         return (first, first_bias), mids, (w_heads @ cpu(last.weight), w_heads @ cpu(last.bias) + b_heads)
+
+
+def _folded_layer(folded, device):
+    """mdx_mlp_t.folded_input / folded_output: one (W, b) of _folded_matrices as [quad image | bias], rounded once; None stays."""
+    if folded is None:
+        return None
+    return torch.cat([_quad_image(folded[0]), folded[1]]).to(device=device, dtype=F32).contiguous()
 
 
 def _pad_folded_layers(network, m, device):
@@ -825,8 +819,8 @@ def _pad_folded_layers(network, m, device):
     n_out = m.number_of_atoms * m.num_classes + m.number_of_atoms * d + d * (d + 1) // 2
     if m.hidden_size > 64 or m.number_of_atoms > 8 or not 2 <= n_hidden <= 4 or n_out > 64 or n_in > 192:
         return None
-    (w_first, b_first), mids, (w_out, b_out) = _folded_matrices(network, m)
-    if w_first.shape[1] != n_in:
+    first, mids, out = _folded_matrices(network, m)
+    if first is None or first[0].shape[1] != n_in:
         return None
 
     def padded(w, b, inputs):
@@ -836,10 +830,9 @@ def _pad_folded_layers(network, m, device):
         bp[: b.shape[0]] = b
         return [_quad_image(wp), bp]
 
-    parts = padded(w_first, b_first, 64 * ((n_in + 63) // 64))
-    for w, b in mids:
+    parts = padded(*first, 64 * ((n_in + 63) // 64))
+    for w, b in mids + [out]:
         parts += padded(w, b, 64)
-    parts += padded(w_out, b_out, 64)
     return torch.cat(parts).to(device=device, dtype=F32).contiguous()
 
 
@@ -850,24 +843,6 @@ def _quad_image(matrix64: torch.Tensor) -> torch.Tensor:
     padded = torch.zeros(n_out, quads * 4, dtype=matrix64.dtype)
     padded[:, :n_in] = matrix64
     return padded.t().reshape(quads, 4, n_out).permute(0, 2, 1).contiguous().reshape(-1)
-
-
-def _fold_output_layers(network, device):
-    """The last hidden layer (no activation follows it, mlp_score_network.py:337-344) folded into the three output
-    heads (mdx_mlp_t.folded_output): outputs ordered logits | score_x | score_l.  Needs >= 2 hidden layers."""
-    if len(network.mlp_layers) < 2:
-        return None
-    f64 = torch.float64
-    with torch.no_grad():
-        last = network.mlp_layers[-1]
-        w_last, b_last = last.weight.detach().to(f64).cpu(), last.bias.detach().to(f64).cpu()
-        heads = (network.output_A_layer, network.output_X_layer, network.output_L_layer)
-        w_heads = torch.cat([h.weight.detach().to(f64).cpu() for h in heads], dim=0)        # [N C + N d + nl, H]
-        b_heads = torch.cat([h.bias.detach().to(f64).cpu() for h in heads], dim=0)
-        folded = w_heads @ w_last                                                           # [outputs, H_in of last]
-        bias = w_heads @ b_last + b_heads
-        return torch.cat([_quad_image(folded), bias]).to(device=device, dtype=F32).contiguous()
-
 
 
 def mlp_forward(pack: MlpPack, atom_types, x, l, time, sigma):
@@ -1076,13 +1051,46 @@ def _pad1(v: torch.Tensor, n: int) -> torch.Tensor:
     return _pad2(v.reshape(1, -1), 1, n).reshape(-1)
 
 
-class EdgeChainPack:
-    """Device image of one E_GCL layer's per-edge MLP chain for mdx_egnn_edge_chain: the H -> H weight matrices of the
-    message MLP (after its first layer) and of the coordinate MLP, re-laid out by mdx_egnn_chain_pack for `precision`,
-    plus the small vectors.  Built from the modules' parameters at construction; `stamp` tells when to rebuild.
-    scales (ActivationScales, optional): shared with the layer's packs of the other precisions.
+def parameter_stamp(*tensors) -> tuple:
+    """((storage address, version), ...) of the given tensors, None skipped: differs once a parameter was replaced or written
+    in place, which is when whatever was built from the parameters has to be rebuilt."""
+    return tuple((t.data_ptr(), t._version) for t in tensors if t is not None)
 
-    Widths.  The kernel runs square layers of one width H in {32, 64, 128, 256}.  A message MLP of width m and a coordinate
+
+class ChainPack:
+    """What the device images of a chain of H x H layers share (mdx_egnn_chain_t): the checks at construction, the weight image
+    re-laid out by mdx_egnn_chain_pack for `precision` with its per-layer exponents, the bias rows, the activation scales and
+    the C struct.  Built from the modules' parameters at construction; the owner's stamp tells when to rebuild.
+    scales (ActivationScales, optional): shared with the owner's packs of the other precisions."""
+
+    def __init__(self, precision: str, scales, supported: bool, not_covered: str):
+        if precision not in EDGE_CHAIN_PRECISIONS:
+            raise _hip.MdxError(f"chain precision must be one of {sorted(EDGE_CHAIN_PRECISIONS)}; got {precision!r}")
+        if not supported:
+            raise _hip.MdxError(not_covered)
+        self.precision, self.scales = precision, scales
+
+    def _build(self, H: int, weights, biases, n_message_layers: int, n_coord_layers: int = 0, w_out=None, tied_layers: int = 0,
+               edge_vectors=(None, None), attention=(None, None)):
+        """weights: the image's [H, H] matrices (w_out [H]: the optional head row); biases: one [H] row per chain layer;
+        edge_vectors / attention: the edge chain's (bias_in, w_radial) / (att_w, att_b)."""
+        self.hidden, self.device = H, weights[0].device
+        self.image, self.exponents = _pack_chain_image(weights, w_out, H, self.precision, tied_layers)
+        self.biases = torch.stack(biases).contiguous()
+        assert self.scales is None or self.scales.count == n_message_layers + n_coord_layers + 2
+        act = self.scales.pointers(self.precision) if self.scales is not None else (None, None)
+        self.c_struct = _hip.EgnnChain(H, n_message_layers, n_coord_layers, EDGE_CHAIN_PRECISIONS[self.precision], 0, 0,
+                                       self.image.data_ptr(), self.biases.data_ptr(),
+                                       *(None if t is None else t.data_ptr() for t in edge_vectors),
+                                       self.exponents.data_ptr(), *act,
+                                       *(None if t is None else t.data_ptr() for t in attention))
+
+
+class EdgeChainPack(ChainPack):
+    """Device image of one E_GCL layer's per-edge MLP chain for mdx_egnn_edge_chain: the H -> H weight matrices of the
+    message MLP (after its first layer) and of the coordinate MLP, plus the small vectors.
+
+    Widths.  The kernel runs square layers of one width H in CHAIN_WIDTHS.  A message MLP of width m and a coordinate
     MLP of width c (the reference's DEFAULT hyper-parameters are m = 16, c = 32: models/score_networks/egnn_score_network.py:
     23-45) run at H = chain_width(m, c) with every matrix, bias and vector ZERO-PADDED: a padded neuron has zero weights and a
     zero bias, so its pre-activation is 0, SiLU(0) = 0, and it feeds zeros on -- the same function, bit for bit in exact
@@ -1092,46 +1100,33 @@ class EdgeChainPack:
     def __init__(self, first_message_layer, message_layers, coord_layers, coord_out_layer, input_size: int, precision: str,
                  scales=None, attention_layer=None):
         """attention_layer: E_GCL.att_mlp's nn.Linear(m, 1) (its Sigmoid is the kernel's), or None."""
-        dev = first_message_layer.weight.device
         message_layers, coord_layers = list(message_layers), list(coord_layers)
         layers = message_layers + coord_layers
-        if precision not in EDGE_CHAIN_PRECISIONS:
-            raise _hip.MdxError(f"edge-chain precision must be one of {sorted(EDGE_CHAIN_PRECISIONS)}; got {precision!r}")
-        if not self.supported(first_message_layer, message_layers, coord_layers, coord_out_layer):
-            raise _hip.MdxError("this E_GCL shape is not covered by the fused edge chain (see mdx_egnn_edge_chain)")
+        super().__init__(precision, scales, self.supported(first_message_layer, message_layers, coord_layers, coord_out_layer),
+                         "this E_GCL shape is not covered by the fused edge chain (see mdx_egnn_edge_chain)")
         m = first_message_layer.out_features
         H = chain_width(m, coord_out_layer.in_features)
-        self.precision, self.hidden, self.message_width = precision, H, m
-        self.image, self.exponents = _pack_chain_image([_pad2(layer.weight, H, H) for layer in layers],
-                                                       _pad1(coord_out_layer.weight, H), H, precision)
-        self.biases = torch.stack([_pad1(layer.bias, H) for layer in layers]).contiguous()
+        self.message_width = m
         self.bias_in = _pad1(first_message_layer.bias, H)
         self.w_radial = _pad1(first_message_layer.weight.detach()[:, 2 * input_size], H)
         # [2H, n_in]: the per-node projections of the first message layer (source half | destination half) as ONE matrix
         w0 = first_message_layer.weight.detach().to(F32)
         self.proj_weight = torch.cat([_pad2(w0[:, :input_size], H, input_size),
                                       _pad2(w0[:, input_size:2 * input_size], H, input_size)], dim=0).contiguous()
-        self.scales = scales
-        act = scales.pointers(precision) if scales is not None else (None, None)
-        assert scales is None or scales.count == len(layers) + 2
         self.att_w = self.att_b = None
         if attention_layer is not None:
             if attention_layer.in_features != m or attention_layer.out_features != 1 or attention_layer.bias is None:
                 raise _hip.MdxError("the attention gate of the fused edge chain is nn.Linear(message width, 1) with a bias")
             self.att_w = _pad1(attention_layer.weight, H)
             self.att_b = attention_layer.bias.detach().to(F32).reshape(-1).contiguous()
-        self.c_struct = _hip.EgnnChain(H, len(message_layers), len(coord_layers),
-                                       EDGE_CHAIN_PRECISIONS[precision], 0, 0, self.image.data_ptr(),
-                                       self.biases.data_ptr(), self.bias_in.data_ptr(), self.w_radial.data_ptr(),
-                                       self.exponents.data_ptr(), *act,
-                                       None if self.att_w is None else self.att_w.data_ptr(),
-                                       None if self.att_b is None else self.att_b.data_ptr())
+        self._build(H, [_pad2(layer.weight, H, H) for layer in layers], [_pad1(layer.bias, H) for layer in layers],
+                    len(message_layers), len(coord_layers), w_out=_pad1(coord_out_layer.weight, H),
+                    edge_vectors=(self.bias_in, self.w_radial), attention=(self.att_w, self.att_b))
         # the kernel's LDS: weight ring + small vectors + per-layer scale table + the source ids of the in-kernel aggregation
         # (+ the attention gate's weight row)
         lds = 4 * 32 * H * 4 + 4 * (len(layers) * H + 2 * H) + 16 * (_hip.EGNN_CHAIN_MAX_LAYERS + 4) + 4 * 4 * 32 + 4 * (_hip.EGNN_CHAIN_MAX_LAYERS + 2) + \
             (16 + 4 * (H + 4) if self.att_w is not None else 0)
         self.piece_sums_ok = lds <= 160 * 1024
-        self.device = dev
 
     @staticmethod
     def supported(first_message_layer, message_layers, coord_layers, coord_out_layer) -> bool:
@@ -1150,26 +1145,15 @@ class EdgeChainPack:
                 coord_out_layer.out_features == 1 and coord_out_layer.bias is None)
 
 
-class RowChainPack:
+class RowChainPack(ChainPack):
     """Device image of a chain of H -> H nn.Linear layers applied to the rows of a matrix (mdx_mlp_chain_rows): every layer
     but the last is followed by SiLU.  Used for the per-node MLP of an EGNN layer after its first (2H -> H) layer."""
 
     def __init__(self, layers, precision: str, scales=None):
         layers = list(layers)
-        H = layers[0].in_features
-        if precision not in EDGE_CHAIN_PRECISIONS:
-            raise _hip.MdxError(f"chain precision must be one of {sorted(EDGE_CHAIN_PRECISIONS)}; got {precision!r}")
-        if not self.supported(layers):
-            raise _hip.MdxError("this layer stack is not covered by mdx_mlp_chain_rows")
-        dev = layers[0].weight.device
-        self.precision, self.hidden = precision, H
-        self.image, self.exponents = _pack_chain_image([layer.weight for layer in layers], None, H, precision)
-        self.biases = torch.stack([layer.bias.detach().to(F32) for layer in layers]).contiguous()
-        self.scales = scales
-        act = scales.pointers(precision) if scales is not None else (None, None)
-        assert scales is None or scales.count == len(layers) + 2
-        self.c_struct = _hip.EgnnChain(H, len(layers), 0, EDGE_CHAIN_PRECISIONS[precision], 0, 0, self.image.data_ptr(),
-                                       self.biases.data_ptr(), None, None, self.exponents.data_ptr(), *act, None, None)
+        super().__init__(precision, scales, self.supported(layers), "this layer stack is not covered by mdx_mlp_chain_rows")
+        self._build(layers[0].in_features, [layer.weight for layer in layers],
+                    [layer.bias.detach().to(F32) for layer in layers], len(layers))
 
     @staticmethod
     def supported(layers) -> bool:
@@ -1177,11 +1161,11 @@ class RowChainPack:
         if not layers:
             return False
         H = layers[0].in_features
-        return (H in (32, 64, 128, 256) and len(layers) <= _hip.EGNN_CHAIN_MAX_LAYERS and
+        return (H in CHAIN_WIDTHS and len(layers) <= _hip.EGNN_CHAIN_MAX_LAYERS and
                 all(l.in_features == H and l.out_features == H and l.bias is not None for l in layers))
 
 
-class NodeMlpPack:
+class NodeMlpPack(ChainPack):
     """Device image of a whole EGNN node MLP -- Linear(2H, H), SiLU, [Linear(H, H), SiLU]*, Linear(H, H) -- for
     mdx_node_mlp_rows: the first layer's [H, 2H] weight as two H x H chain layers."""
 
@@ -1190,13 +1174,8 @@ class NodeMlpPack:
         two H x H halves follow the MLP in the image, and node_mlp_rows also returns out @ next_projection.T.
         scales: ActivationScales(n_chain_layers(layers), device), shared between the precisions."""
         layers = list(layers)
-        if precision not in EDGE_CHAIN_PRECISIONS:
-            raise _hip.MdxError(f"chain precision must be one of {sorted(EDGE_CHAIN_PRECISIONS)}; got {precision!r}")
-        if not self.supported(layers):
-            raise _hip.MdxError("this layer stack is not covered by mdx_node_mlp_rows")
+        super().__init__(precision, scales, self.supported(layers), "this layer stack is not covered by mdx_node_mlp_rows")
         H = layers[0].out_features
-        dev = layers[0].weight.device
-        self.precision, self.hidden = precision, H
         w0 = layers[0].weight.detach().to(F32)
         keep = [w0[:, :H].contiguous(), w0[:, H:].contiguous()] + [l.weight.detach().to(F32).contiguous() for l in layers[1:]]
         n = len(keep)
@@ -1207,15 +1186,9 @@ class NodeMlpPack:
         # tied: the two halves of the wide first layer (their accumulators continue one another) and the two halves of the
         # projection share a power of two each
         tied = (1 << 1) | ((1 << (n + 1)) if self.projects else 0)
-        self.image, self.exponents = _pack_chain_image(keep, None, H, precision, tied_layers=tied)
-        zeros = torch.zeros(H, dtype=F32, device=dev)
-        self.biases = torch.stack([layers[0].bias.detach().to(F32), zeros] +
-                                  [l.bias.detach().to(F32) for l in layers[1:]]).contiguous()
-        self.scales = scales
-        act = scales.pointers(precision) if scales is not None else (None, None)
-        assert scales is None or scales.count == n + 2
-        self.c_struct = _hip.EgnnChain(H, n, 0, EDGE_CHAIN_PRECISIONS[precision], 0, 0, self.image.data_ptr(),
-                                       self.biases.data_ptr(), None, None, self.exponents.data_ptr(), *act)
+        zeros = torch.zeros(H, dtype=F32, device=w0.device)
+        self._build(H, keep, [layers[0].bias.detach().to(F32), zeros] + [l.bias.detach().to(F32) for l in layers[1:]], n,
+                    tied_layers=tied)
 
     @staticmethod
     def n_chain_layers(layers) -> int:
@@ -1228,7 +1201,7 @@ class NodeMlpPack:
         if len(layers) < 2:
             return False
         H = layers[0].out_features
-        return (H in (32, 64, 128, 256) and layers[0].in_features == 2 * H and len(layers) + 1 <= _hip.EGNN_CHAIN_MAX_LAYERS and
+        return (H in CHAIN_WIDTHS and layers[0].in_features == 2 * H and len(layers) + 1 <= _hip.EGNN_CHAIN_MAX_LAYERS and
                 all(l.in_features == H and l.out_features == H for l in layers[1:]) and all(l.bias is not None for l in layers))
 
 

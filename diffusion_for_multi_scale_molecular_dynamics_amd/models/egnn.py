@@ -28,6 +28,7 @@ from typing import Callable, Optional, Tuple
 import torch
 from torch import nn
 
+from .. import kernels
 from ..namespace import AXL
 
 
@@ -45,6 +46,35 @@ def segment_sum_sorted(data: torch.Tensor, degree: torch.Tensor) -> torch.Tensor
 
     Replaces unsorted_segment_sum (src/.../models/egnn_utils.py:11-38) for sorted edge lists."""
     return torch.segment_reduce(data, "sum", lengths=degree, axis=0, unsafe=True)
+
+
+class LayerDeviceState:
+    """Everything an E_GCL owns on the device for the fused path; plain Python, one object per layer, never copied or
+    pickled with it (the packs hold raw pointers: a copy of the layer starts with an empty one and rebuilds on first use).
+      packs      kind ("edge", "rows", "node") -> precision -> (stamp, pack): one kernels.EdgeChainPack / RowChainPack /
+                 NodeMlpPack per precision
+      in_use     kind -> (stamp, pack): what the last request of that kind selected
+      scales     (kind, n_layers, device) -> kernels.ActivationScales, shared by the kind's packs of every precision
+      memos      the kernels.EgnnTableMemo of the layer as a first graph layer, by shape, device and precision;
+                 memo_used: the one the last table forward ran on; table_worst: its midpoint-check result (device)"""
+    KINDS = ("edge", "rows", "node")
+
+    def __init__(self):
+        self.packs = {kind: {} for kind in self.KINDS}
+        self.in_use = {kind: (None, None) for kind in self.KINDS}
+        self.scales, self.memos = {}, {}
+        self.memo_used = self.table_worst = None
+
+    def pack(self, kind: str, precision: str, stamp, build):
+        """The pack of `kind` for `precision` and `stamp`, from build() when none is kept.  A pack a captured iteration may
+        point at is never freed by a precision switch: the generator's one-iteration switch to "f32" and back selects among
+        the kept entries and repacks nothing, and only a new stamp replaces an entry -- that of its own precision."""
+        if self.in_use[kind][0] != stamp:
+            kept = self.packs[kind]
+            if kept.get(precision, (None, None))[0] != stamp:
+                kept[precision] = (stamp, build())
+            self.in_use[kind] = kept[precision]
+        return self.in_use[kind][1]
 
 
 class E_GCL(nn.Module):
@@ -71,9 +101,7 @@ class E_GCL(nn.Module):
         # "f32" (exact binary32 MFMA) or None (per-layer library GEMMs)
         self.edge_chain_precision = "f16x3"
         self.status_word = None          # device int32 word for MDX_STATUS_EGNN_F16_RANGE (set by the score network)
-        self._chain = (None, None)       # (stamp, kernels.EdgeChainPack)
-        self._node_chain = (None, None)  # (stamp, kernels.RowChainPack): the node MLP after its first layer
-        self._node_mlp = (None, None)    # (stamp, kernels.NodeMlpPack): the whole node MLP
+        self._device_state = LayerDeviceState()
 
         mh, nh, ch = message_hidden_dimensions_size, node_hidden_dimensions_size, coordinate_hidden_dimensions_size
         layers = [nn.Linear(2 * input_size + 1, mh), act_fn]
@@ -99,26 +127,32 @@ class E_GCL(nn.Module):
             self.att_mlp = nn.Sequential(nn.Linear(mh, 1), nn.Sigmoid())
 
     def __getstate__(self):
-        """Copies and pickles of the module (copy.deepcopy, torch.save of a whole model) carry no device images: the packs
-        hold raw pointers and are rebuilt on first use."""
-        state = dict(self.__dict__)
-        state["_chain"], state["_node_chain"], state["status_word"] = (None, None), (None, None), None
-        state["_node_mlp"] = (None, None)
-        state.pop("_chain_kept", None)
-        state.pop("_node_mlp_kept", None)
-        state.pop("_node_chain_kept", None)
-        state.pop("_activation_scales", None)
-        state.pop("_table_memos", None)
-        state.pop("_table_memo_used", None)
-        state.pop("table_worst", None)
+        """Copies and pickles of the module (copy.deepcopy, torch.save of a whole model) carry no device state."""
+        return {**self.__dict__, "_device_state": LayerDeviceState(), "status_word": None}
+
+    @property
+    def device_state(self) -> LayerDeviceState:
+        """(created here for a module unpickled without one: an older pickle, or the reference's)"""
+        state = self.__dict__.get("_device_state")
+        if state is None:
+            state = self.__dict__["_device_state"] = LayerDeviceState()
         return state
+
+    # (stamp, pack) of the kernels.EdgeChainPack, the RowChainPack (the node MLP after its first layer) and the NodeMlpPack (the
+    # whole node MLP) the last forward selected; (None, None) before the first
+    _chain = property(lambda self: self.device_state.in_use["edge"])
+    _node_chain = property(lambda self: self.device_state.in_use["rows"])
+    _node_mlp = property(lambda self: self.device_state.in_use["node"])
+    _node_chain_kept = property(lambda self: self.device_state.packs["rows"])
+    _activation_scales = property(lambda self: self.device_state.scales)
+    _table_memos = property(lambda self: self.device_state.memos)
+    table_worst = property(lambda self: self.device_state.table_worst)
 
     def _scales(self, kind: str, n_layers: int, device):
         """kernels.ActivationScales of one of the layer's chains ("edge", "node", "rows"): the per-position powers of two of
         the split-f16 kernels and the maxima the exact-f32 kernels collect, shared by the chain's packs of every precision
         and kept across repacks (an exponent only ever goes down)."""
-        from .. import kernels
-        kept = self.__dict__.setdefault("_activation_scales", {})
+        kept = self.device_state.scales
         key = (kind, n_layers, str(device))
         if key not in kept:
             kept[key] = kernels.ActivationScales(n_layers, device)
@@ -127,19 +161,19 @@ class E_GCL(nn.Module):
     def adapt_f16_range(self):
         """After an exact-f32 pass (the generator's answer to an f16-range report): turn the maxima that pass collected into
         activation exponents for the split-f16 kernels (device-side, no host read)."""
-        for scales in self.__dict__.get("_activation_scales", {}).values():
+        for scales in self.device_state.scales.values():
             scales.adapt()
         self.reset_table_memos()
 
     def begin_f16_range_fallback(self):
         """Before the exact-f32 pass of a fallback: forget the maxima earlier f32 launches have left."""
-        for scales in self.__dict__.get("_activation_scales", {}).values():
+        for scales in self.device_state.scales.values():
             scales.maxima.zero_()
         self.reset_table_memos()       # (a skipped build would also skip its share of the maxima)
 
     def reset_f16_range(self):
         """Back to the default activation exponents (and no collected maxima): what a freshly built layer has."""
-        for scales in self.__dict__.get("_activation_scales", {}).values():
+        for scales in self.device_state.scales.values():
             scales.reset()
         self.reset_table_memos()
 
@@ -148,28 +182,27 @@ class E_GCL(nn.Module):
         captured iteration holds its pointers).  `stamp`: whatever the table's arithmetic depends on besides sigma and the
         activation exponents -- this layer's pack is added here; when it differs from the stamp of the last call, the key is
         reset (a fill on the stream)."""
-        from .. import kernels
-        memos = self.__dict__.setdefault("_table_memos", {})
+        state = self.device_state
         key = (pack.precision, n_classes, n_even, pack.hidden, embedding_width, coord_dimension, str(device))
-        memo = memos.get(key)
+        memo = state.memos.get(key)
         if memo is None:
-            memo = memos[key] = kernels.EgnnTableMemo(n_classes, n_even, pack.hidden, embedding_width, coord_dimension, device)
+            memo = state.memos[key] = kernels.EgnnTableMemo(n_classes, n_even, pack.hidden, embedding_width, coord_dimension, device)
         stamp = (self._chain[0], stamp)
-        if memo.stamp != stamp or self.__dict__.get("_table_memo_used") is not memo:
+        if memo.stamp != stamp or state.memo_used is not memo:
             # (also after a forward of another precision: the switch to "f32" and back around a range report)
             if memo.stamp is not None:
                 memo.reset()
             memo.stamp = stamp
-            self._table_memo_used = memo
+            state.memo_used = memo
         return memo
 
     def table_builds(self) -> int:
         """Distance tables built so far by this layer, over all its memos (host reads: tests and evidence)."""
-        return sum(memo.builds() for memo in self.__dict__.get("_table_memos", {}).values())
+        return sum(memo.builds() for memo in self.device_state.memos.values())
 
     def reset_table_memos(self):
         """Forget every kept distance table (the activation exponents or maxima changed, or the caller wants a fresh build)."""
-        for memo in self.__dict__.get("_table_memos", {}).values():
+        for memo in self.device_state.memos.values():
             memo.reset()
 
     def _messages(self, h: torch.Tensor, edge_index: torch.Tensor, radial: torch.Tensor, fused: bool) -> torch.Tensor:
@@ -181,7 +214,6 @@ class E_GCL(nn.Module):
         proj = torch.nn.functional.linear(h, torch.cat([w[:, :n_in], w[:, n_in:2 * n_in]], dim=0))
         rest = list(self.message_mlp)[1:]
         if fused and mh % 4 == 0 and isinstance(rest[0], nn.SiLU):
-            from .. import kernels
             out = kernels.egnn_message_input(proj.contiguous(), edge_index, radial.reshape(-1).contiguous(), first.bias,
                                              w[:, 2 * n_in].contiguous(), silu=True)
             rest = rest[1:]
@@ -259,78 +291,59 @@ class E_GCL(nn.Module):
         return None
 
     def _coord_flags(self) -> int:
-        from .. import kernels
         return kernels.coord_flags(self.normalize, self.tanh)
 
     def _edge_chain_pack(self):
         """The layer's kernels.EdgeChainPack, rebuilt when a parameter, the device or the precision changed; None when
         the fused kernel does not apply."""
-        if self.edge_chain_precision is None:
-            return None
-        modules = self._chain_modules()
+        precision = self.edge_chain_precision
+        modules = self._chain_modules() if precision is not None else None
         if modules is None:
             return None
-        from .. import kernels
         if not kernels.EdgeChainPack.supported(*modules):
             return None
         attention = self._attention_layer() if self.attention else None
         if attention is not None and attention.in_features != modules[0].out_features:
             return None
         linears = [modules[0], *modules[1], *modules[2], modules[3]] + ([attention] if attention is not None else [])
-        stamp = (self.edge_chain_precision,) + tuple((t.data_ptr(), t._version) for lin in linears
-                                                      for t in (lin.weight, lin.bias) if t is not None)
-        if self._chain[0] != stamp:
-            # (one image per precision is kept: the generator's one-call switch to "f32" and back repacks nothing)
-            kept = self.__dict__.setdefault("_chain_kept", {})
-            if kept.get(self.edge_chain_precision, (None, None))[0] != stamp:
-                n_layers = len(list(modules[1])) + len(list(modules[2]))
-                kept[self.edge_chain_precision] = (stamp, kernels.EdgeChainPack(
-                    *modules, input_size=self.input_size, precision=self.edge_chain_precision,
-                    scales=self._scales("edge", n_layers, modules[0].weight.device), attention_layer=attention))
-            self._chain = kept[self.edge_chain_precision]
-        if attention is not None and not self._chain[1].piece_sums_ok:
+        stamp = (precision,) + kernels.parameter_stamp(*(t for lin in linears for t in (lin.weight, lin.bias)))
+        pack = self.device_state.pack("edge", precision, stamp, lambda: kernels.EdgeChainPack(
+            *modules, input_size=self.input_size, precision=precision, attention_layer=attention,
+            scales=self._scales("edge", len(modules[1]) + len(modules[2]), modules[0].weight.device)))
+        if attention is not None and not pack.piece_sums_ok:
             return None          # (the gate is instantiated for the in-kernel message sums only: mdx_egnn_edge_chain)
-        return self._chain[1]
+        return pack
+
+    def _node_linears(self):
+        """The node MLP's nn.Linear layers when the fused path is on and the stack is Linear / SiLU alternation ending in a
+        Linear (two Linears at least), else None."""
+        node = list(self.node_mlp)
+        if self.edge_chain_precision is None or len(node) < 3 or len(node) % 2 == 0:
+            return None
+        linears, acts = node[0::2], node[1::2]
+        if not all(isinstance(lin, nn.Linear) for lin in linears) or not all(isinstance(a, nn.SiLU) for a in acts):
+            return None
+        return linears
 
     def _node_chain_pack(self):
         """kernels.RowChainPack of the node MLP's H -> H layers (all but its first, 2H -> H, layer), or None when the stack
         is not Linear / SiLU alternation of equal widths ending in a Linear."""
-        if self.edge_chain_precision is None:
-            return None
-        node = list(self.node_mlp)
-        if len(node) < 3 or len(node) % 2 == 0:
-            return None
-        linears, acts = node[0::2], node[1::2]
-        if not all(isinstance(lin, nn.Linear) for lin in linears) or not all(isinstance(a, nn.SiLU) for a in acts):
+        linears = self._node_linears()
+        if linears is None:
             return None
         rest = linears[1:]
-        from .. import kernels
         if linears[0].out_features != rest[0].in_features or not kernels.RowChainPack.supported(rest):
             return None
-        stamp = (self.edge_chain_precision,) + tuple((t.data_ptr(), t._version) for lin in rest for t in (lin.weight, lin.bias))
-        if self._node_chain[0] != stamp:
-            # one image per precision is KEPT, like the other two packs: a captured iteration has the split-f16 image's
-            # pointers in its kernel arguments, and the generator's one-iteration switch to "f32" and back must not free it
-            kept = self.__dict__.setdefault("_node_chain_kept", {})
-            if kept.get(self.edge_chain_precision, (None, None))[0] != stamp:
-                kept[self.edge_chain_precision] = (stamp, kernels.RowChainPack(
-                    rest, self.edge_chain_precision, scales=self._scales("rows", len(rest), rest[0].weight.device)))
-            self._node_chain = kept[self.edge_chain_precision]
-        return self._node_chain[1]
+        precision = self.edge_chain_precision
+        stamp = (precision,) + kernels.parameter_stamp(*(t for lin in rest for t in (lin.weight, lin.bias)))
+        return self.device_state.pack("rows", precision, stamp, lambda: kernels.RowChainPack(
+            rest, precision, scales=self._scales("rows", len(rest), rest[0].weight.device)))
 
     def _node_mlp_pack(self, next_layer=None):
         """kernels.NodeMlpPack of the WHOLE node MLP (Linear(2H, H) first), or None when it does not have that shape; with
         the per-node projections of `next_layer` appended when that layer runs the fused edge chain on the same width."""
-        if self.edge_chain_precision is None:
-            return None
-        node = list(self.node_mlp)
-        if len(node) < 3 or len(node) % 2 == 0:
-            return None
-        linears, acts = node[0::2], node[1::2]
-        if not all(isinstance(lin, nn.Linear) for lin in linears) or not all(isinstance(a, nn.SiLU) for a in acts):
-            return None
-        from .. import kernels
-        if not kernels.NodeMlpPack.supported(linears):
+        linears = self._node_linears()
+        if linears is None or not kernels.NodeMlpPack.supported(linears):
             return None
         next_pack = next_layer._edge_chain_pack() if next_layer is not None and next_layer.use_fused_ops else None
         projection = None
@@ -338,16 +351,11 @@ class E_GCL(nn.Module):
                 and next_pack.hidden == linears[0].out_features and next_pack.message_width == next_pack.hidden:
             projection = next_pack.proj_weight
         first_next = next_layer.message_mlp[0].weight if projection is not None else None
-        stamp = (self.edge_chain_precision,) + tuple((t.data_ptr(), t._version) for lin in linears for t in (lin.weight, lin.bias)) + \
-            ((first_next.data_ptr(), first_next._version) if first_next is not None else (None,))
-        if self._node_mlp[0] != stamp:
-            kept = self.__dict__.setdefault("_node_mlp_kept", {})
-            if kept.get(self.edge_chain_precision, (None, None))[0] != stamp:
-                kept[self.edge_chain_precision] = (stamp, kernels.NodeMlpPack(
-                    linears, self.edge_chain_precision, next_projection=projection,
-                    scales=self._scales("node", kernels.NodeMlpPack.n_chain_layers(linears), linears[0].weight.device)))
-            self._node_mlp = kept[self.edge_chain_precision]
-        return self._node_mlp[1]
+        precision = self.edge_chain_precision
+        stamp = (precision,) + kernels.parameter_stamp(*(t for lin in linears for t in (lin.weight, lin.bias)), first_next)
+        return self.device_state.pack("node", precision, stamp, lambda: kernels.NodeMlpPack(
+            linears, precision, next_projection=projection,
+            scales=self._scales("node", kernels.NodeMlpPack.n_chain_layers(linears), linears[0].weight.device)))
 
     def _coord_head_is_plain(self) -> bool:
         last = self.coord_mlp[-1]
@@ -395,7 +403,6 @@ class E_GCL(nn.Module):
 
         segments = fused and offsets is not None and messages.shape[1] % 4 == 0
         if segments and self._coord_head_is_plain():
-            from .. import kernels
             hidden = run_mlp(list(self.coord_mlp)[:-1], messages, fused)
             coord = coord + kernels.egnn_coord_head(hidden.contiguous(), self.coord_mlp[-1].weight.reshape(-1),
                                                     coord_diff.contiguous(), offsets, degree, self.coords_mean)
@@ -404,7 +411,6 @@ class E_GCL(nn.Module):
             coord = coord + (trans / count if self.coords_mean else trans)
 
         if segments:
-            from .. import kernels
             agg = kernels.segment_rows(messages.contiguous(), offsets, degree, self.message_mean)
         else:
             agg = segment_sum_sorted(messages, degree)
@@ -427,14 +433,13 @@ class E_GCL(nn.Module):
         """egnn_node_gather's ([left | message sums] or the sums, coord_out) with the per-edge chain replaced by the chain on the
         distance grid (kernels.egnn_table_grid), its midpoint check (MDX_STATUS_EGNN_TABLE into the status word when it fails
         or sigma is not uniform) and the interpolating gather.  Fixed sizes, no host read: capture-safe."""
-        from .. import kernels
         _, grid_coord, grid_edges = kernels.egnn_table_grid(table.n_classes, table.n_even, coord.shape[1], coord.device)
         memo = table.memo
         # the table kept on the device: the chain and the midpoint check return at once while the memo's key holds this forward's
         # sigma; the uniform-sigma check runs regardless (kernels.EgnnTableMemo)
         values, scalars = kernels.egnn_edge_chain(pack, memo.grid_proj, grid_coord, grid_edges, status=self.status_word,
                                                   memo=memo, sigma=table.sigma)
-        self.table_worst = memo.worst
+        self.device_state.table_worst = memo.worst
         kernels.egnn_table_check(values, scalars, table.n_classes, table.n_even, table.sigma, memo.workspace,
                                  worst=memo.worst, status=self.status_word, key=memo.key)
         return kernels.egnn_table_gather(values, scalars, table.n_classes, table.n_even, table.atom_types, offsets, degree,
@@ -446,7 +451,6 @@ class E_GCL(nn.Module):
         """E_GCL.forward with the per-edge work in one MFMA kernel: node projections (library GEMM, per node) -> fused
         chain -> the two sorted-segment reductions -> node MLP.  With `table` (and table_applies) the per-edge chain and the
         node gather are _table_gather."""
-        from .. import kernels
         coord = coord.contiguous()
         if table is not None and self.table_applies(pack, h, coord):
             def gather(left):
@@ -486,7 +490,6 @@ class E_GCL(nn.Module):
 
     def _node_part(self, h, gather, next_layer):
         """Everything per node after the per-edge work, from gather(left) -> ([left | message sums] or the sums, coord_out)."""
-        from .. import kernels
         whole = self._node_mlp_pack(next_layer)
         if whole is not None and whole.hidden == h.shape[1]:
             # everything per node between the edge chain and the node MLP in one pass (the message sums and the updated
@@ -504,7 +507,6 @@ class E_GCL(nn.Module):
 
     def _node_mlp_tail(self, h, node_in, coord_out):
         """The node MLP on node_in = [h | agg] and the residual."""
-        from .. import kernels
         node_pack = self._node_chain_pack()
         if node_pack is not None and (not self.residual or h.shape[1] == node_pack.hidden):
             # first node layer (2H -> H, + SiLU): a PyTorch matmul per node; the other layers and the residual: one MFMA launch

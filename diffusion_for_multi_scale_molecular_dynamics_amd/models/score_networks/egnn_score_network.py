@@ -198,6 +198,7 @@ class EGNNScoreNetwork(ScoreNetwork):
         the embedded inputs are then a linear map of [sigma | one_hot] like the embedding itself (no [n_nodes, H] x [H, 2H]
         product per forward).  None when the first layer does not run the fused edge chain.  Cached on the parameters'
         versions."""
+        from ... import kernels
         layers = self.egnn.graph_layers
         if len(layers) == 0 or not layers[0].use_fused_ops:
             return None
@@ -206,7 +207,7 @@ class EGNNScoreNetwork(ScoreNetwork):
         if pack is None or pack.proj_weight.shape[1] != emb.out_features:
             return None
         first = layers[0].message_mlp[0].weight
-        stamp = tuple((t.data_ptr(), t._version) for t in (first, emb.weight, emb.bias)) + (layers[0].edge_chain_precision,)
+        stamp = kernels.parameter_stamp(first, emb.weight, emb.bias) + (layers[0].edge_chain_precision,)
         if getattr(self, "_first_projection", (None, None))[0] != stamp:
             with torch.no_grad():
                 w2 = (pack.proj_weight.double() @ emb.weight.double()).float().contiguous()
@@ -242,7 +243,7 @@ class EGNNScoreNetwork(ScoreNetwork):
         sigma = sigma.to(device=z.device, dtype=torch.float32).reshape(-1).contiguous()
         emb = self.egnn.embedding_in
         # the memo's stamp: the inputs of the grid's node projections (the layer adds its own pack) -- a change resets the key
-        stamp = tuple((t.data_ptr(), t._version) for t in (emb.weight, emb.bias, *second))
+        stamp = kernels.parameter_stamp(emb.weight, emb.bias, *second)
         memo = layer.table_memo(layer._edge_chain_pack(), n_classes, n_even, emb.out_features, z.shape[1], z.device, stamp)
         if not self.first_layer_table_reuse:
             memo.reset()
