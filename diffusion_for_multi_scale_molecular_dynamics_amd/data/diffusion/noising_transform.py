@@ -24,7 +24,9 @@ class NoisingTransform:
                  use_fixed_lattice_parameters: bool = False, use_optimal_transport: bool = True, device="cuda"):
         """The reference's signature and defaults (:37-44) + `device`.  Optimal transport (the default there) re-assigns atoms
         while noising a TRAINING batch: outside the sampling hot path, refused loudly rather than silently skipped -- the
-        sampling path passes use_optimal_transport=False (generators/constrained_langevin_generator.py:71)."""
+        sampling path passes use_optimal_transport=False (generators/constrained_langevin_generator.py:71).  (The call the
+        reference makes there, Transporter(identity).get_optimal_transport(x0, xt), exists in transport/transporter.py; this
+        transform is not wired to it: tests/test_generator_gpu.py pins the refusal.)"""
         if use_optimal_transport:
             raise NotImplementedError("NoisingTransform(use_optimal_transport=True) is the training-time augmentation, outside "
                                       "this package's scope: pass use_optimal_transport=False (as the repaint generator does)")

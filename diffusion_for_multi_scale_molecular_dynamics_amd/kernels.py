@@ -692,6 +692,83 @@ def analytical_score(relative_coordinates, sigmas, equilibrium_relative_coordina
 
 
 # ----------------------------------------------------------------------------------------------------------------
+# linear assignment, optimal transport, equivariant analytical score network (csrc/mdx_transport.hip)
+# ----------------------------------------------------------------------------------------------------------------
+TRANSPORT_MAX_ATOMS, TRANSPORT_MAX_OPERATIONS = _hip.TRANSPORT_MAX_ATOMS, _hip.TRANSPORT_MAX_OPERATIONS
+
+
+def linear_assignment(cost_matrices, status: Optional[torch.Tensor] = None):
+    """(col_idx int32 [M, n], costs f64 [M]) of the M assignment problems cost_matrices f32 or f64 [M, n, n], n <= 256
+    (mdx_linear_assignment): col_idx[m, i] is the column of row i, costs[m] the optimum summed in row order.  A matrix with a
+    non-finite entry gives col_idx -1, a NaN cost and STATUS_LAP_COST in `status`."""
+    _device_only("the linear assignment", cost_matrices=cost_matrices, status=status)
+    if cost_matrices.dim() != 3 or cost_matrices.shape[1] != cost_matrices.shape[2]:
+        raise ValueError(f"cost_matrices has shape {tuple(cost_matrices.shape)}, expected [M, n, n]")
+    if cost_matrices.dtype not in (F32, F64):
+        raise TypeError(f"cost_matrices must be float32 or float64, got {cost_matrices.dtype}")
+    M, n, _ = cost_matrices.shape
+    col_idx = torch.empty(M, n, dtype=I32, device=cost_matrices.device)
+    costs = torch.empty(M, dtype=F64, device=cost_matrices.device)
+    check(lib().mdx_linear_assignment(ptr(cost_matrices, cost_matrices.dtype, "cost_matrices"), int(cost_matrices.dtype == F64), M, n,
+                                      ptr(col_idx, I32, "col_idx"), ptr(costs, F64, "costs"), ptr(status, I32, "status"),
+                                      stream_handle()), "mdx_linear_assignment")
+    return col_idx, costs
+
+
+def transport_align(x, mu, point_group_operations, with_details: bool = False, status: Optional[torch.Tensor] = None):
+    """Transporter.get_optimal_transport in one launch (mdx_transport_align): x f32 [B, N, D]; mu f32 [N, D] (shared) or
+    [B, N, D]; point_group_operations f32 [O, D, D].  Returns the aligned image of mu f32 [B, N, D], and with `with_details`
+    also (operation index int32 [B], col_idx int32 [B, N], costs f64 [B, O])."""
+    _device_only("the optimal transport", x=x, mu=mu, point_group_operations=point_group_operations, status=status)
+    B, N, D = x.shape
+    O = point_group_operations.shape[0]
+    if point_group_operations.shape != (O, D, D):
+        raise ValueError(f"point_group_operations has shape {tuple(point_group_operations.shape)}, expected [O, {D}, {D}]")
+    if mu.shape == (N, D):
+        stride = 0
+    elif mu.shape == (B, N, D):
+        stride = N * D
+    else:
+        raise ValueError(f"mu has shape {tuple(mu.shape)}, expected {(N, D)} or {(B, N, D)}")
+    dev = x.device
+    aligned = torch.empty(B, N, D, dtype=F32, device=dev)
+    operation_idx = torch.empty(B, dtype=I32, device=dev) if with_details else None
+    col_idx = torch.empty(B, N, dtype=I32, device=dev) if with_details else None
+    costs = torch.empty(B, O, dtype=F64, device=dev) if with_details else None
+    check(lib().mdx_transport_align(ptr(x, F32, "x"), ptr(mu, F32, "mu"), stride,
+                                    ptr(point_group_operations, F32, "point_group_operations"), O, B, N, D,
+                                    ptr(aligned, F32, "aligned"), ptr(operation_idx, I32, "operation_idx"),
+                                    ptr(col_idx, I32, "col_idx"), ptr(costs, F64, "costs"), ptr(status, I32, "status"),
+                                    stream_handle()), "mdx_transport_align")
+    return (aligned, operation_idx, col_idx, costs) if with_details else aligned
+
+
+def equivariant_analytical_score(relative_coordinates, sigmas, equilibrium_relative_coordinates, point_group_operations,
+                                 sigma_d_square: float, kmax: int, status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The equivariant analytical score network's forward (mdx_equivariant_analytical_score): relative_coordinates f32 [B, N, D];
+    sigmas f32 [B] (numel B); sites f32 [N, D]; point_group_operations f32 [O, D, D].  One kernel, no host read: a structure
+    with an invalid sigma or a non-finite coordinate holds NaNs and its bit is OR-ed into `status`."""
+    _device_only("the equivariant analytical score", relative_coordinates=relative_coordinates, sigmas=sigmas,
+                 equilibrium_relative_coordinates=equilibrium_relative_coordinates, point_group_operations=point_group_operations,
+                 status=status)
+    B, N, D = relative_coordinates.shape
+    O = point_group_operations.shape[0]
+    if equilibrium_relative_coordinates.shape != (N, D):
+        raise ValueError(f"equilibrium_relative_coordinates has shape {tuple(equilibrium_relative_coordinates.shape)}, expected {(N, D)}")
+    if point_group_operations.shape != (O, D, D):
+        raise ValueError(f"point_group_operations has shape {tuple(point_group_operations.shape)}, expected [O, {D}, {D}]")
+    if sigmas.numel() != B:
+        raise ValueError(f"sigmas has shape {tuple(sigmas.shape)}: expected one per structure, [{B}]")
+    scores = torch.empty(B, N, D, dtype=F32, device=relative_coordinates.device)
+    check(lib().mdx_equivariant_analytical_score(ptr(relative_coordinates, F32, "relative_coordinates"), ptr(sigmas, F32, "sigmas"),
+                                                 ptr(equilibrium_relative_coordinates, F32, "equilibrium_relative_coordinates"),
+                                                 ptr(point_group_operations, F32, "point_group_operations"), O,
+                                                 float(sigma_d_square), int(kmax), B, N, D, ptr(scores, F32, "scores"),
+                                                 ptr(status, I32, "status"), stream_handle()), "mdx_equivariant_analytical_score")
+    return scores
+
+
+# ----------------------------------------------------------------------------------------------------------------
 # fused MLP score network
 # ----------------------------------------------------------------------------------------------------------------
 class MlpPack:

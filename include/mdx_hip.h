@@ -66,6 +66,8 @@ extern "C" {
                                             excise_and_random_sample_maker.py:305-308 assert); its samples come out zero     */
 #define MDX_STATUS_RANDOM_FILL_ENVIRONMENT 8192u /* the same function: a sample names an environment outside [0, E), or the
                                             environment's active atom is not one of its constrained atoms; zero likewise  */
+#define MDX_STATUS_LAP_COST 16384u       /* mdx_linear_assignment: a cost that is not finite (|c| >= 1e300 included); that
+                                            problem's col_idx is -1 and its cost NaN                                        */
 
 #define MDX_MAX_CLASSES 8      /* C supported by the fused atom-type kernels */
 #define MDX_PREDICTOR 0
@@ -510,6 +512,49 @@ MDX_API int mdx_analytical_score(const float* relative_coordinates, const float*
                                  const float* equilibrium_relative_coordinates, double sigma_d_square, int kmax,
                                  int use_permutation_invariance, int64_t batch, int number_of_atoms, int spatial_dimension,
                                  float* sigma_normalized_scores, float* probabilities, uint32_t* status, mdx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Linear assignment and optimal transport (csrc/mdx_transport.hip): the reference's transport/transporter.py and its
+ * equivariant analytical score network, which solve their assignment problems one by one on the host
+ * (scipy.optimize.linear_sum_assignment), here in one launch with no host read.  The solver is the shortest-augmenting-path
+ * Hungarian algorithm in binary64, one wavefront per problem, for n <= 256 (else MDX_ERR_UNSUPPORTED).  Among equal values its
+ * arg-min takes the lower column, and it uses no atomics: a launch (or a hipGraph replay) always gives the same bits.  Its loop
+ * counts are bounded by n whatever the data, and invalid input is reported, never a fault. */
+
+/* min over permutations of sum_i cost[i][col_idx[i]] for `problems` matrices [n][n], row-major, f32 (costs_are_f64 0: promoted
+ * once) or f64.  col_idx int32 [problems][n]: the column of each row; costs f64 [problems]: the optimum, summed in row order.
+ * A matrix with an entry that is not finite gives col_idx -1, cost NaN and MDX_STATUS_LAP_COST in status (nullable). */
+MDX_API int mdx_linear_assignment(const void* cost_matrices, int costs_are_f64, int64_t problems, int n, int32_t* col_idx,
+                                  double* costs, uint32_t* status, mdx_stream_t stream);
+
+/* Transporter.get_optimal_transport (transport/transporter.py:148-196), one workgroup per structure.  x f32 [batch, N, D];
+ * mu f32 [N, D] shared by the batch (mu_batch_stride 0) or [batch, N, D] (mu_batch_stride N D; anything else is
+ * MDX_ERR_INVALID_ARG); point_group_operations f32 [O, D, D].  N <= 256, D <= 3, O <= 48, else MDX_ERR_UNSUPPORTED.
+ *   centre   c = atan2(mean_n sin 2 pi x, mean_n cos 2 pi x) / 2 pi per dimension (sums in atom order); x~ = wrap(x - c_x),
+ *            mu~ = wrap(mu - c_mu); wrap(y) = y - floor(y), a fraction that rounds to 1 becomes 0
+ *   solve    per operation o: cost(i, j) = sum_d g^2, g = delta - rint(delta), delta = (R_o mu~)_j - x~_i (the square of the
+ *            reference's atan2(sin, cos) / 2 pi, up to rounding), solved as above
+ *   choose   the first minimum of the O optimal costs, in operation order
+ *   write    aligned_mu [batch, N, D] row n = wrap(R_chosen mu~[col_idx[n]]), rounded once to f32
+ * Optional outputs (NULL: not written): operation_idx int32 [batch], col_idx int32 [batch, N] (of the chosen operation),
+ * costs f64 [batch, O].  A structure with a coordinate that is not finite gets NaN (-1 in the integer outputs) and
+ * MDX_STATUS_ANALYTICAL_COORDINATES in status (nullable); any finite coordinate is accepted. */
+MDX_API int mdx_transport_align(const float* x, const float* mu, int64_t mu_batch_stride, const float* point_group_operations,
+                                int number_of_operations, int64_t batch, int number_of_atoms, int spatial_dimension,
+                                float* aligned_mu, int32_t* operation_idx, int32_t* col_idx, double* costs, uint32_t* status,
+                                mdx_stream_t stream);
+
+/* The equivariant analytical score network's forward (models/score_networks/equivariant_analytical_score_network.py,
+ * get_normalized_scores): the alignment above of the shared equilibrium sites [N, D] onto each structure, then per element
+ * u = wrap(x~ - aligned image), s = sqrt(sigma_d_square + sigma^2) and sigma_normalized_scores = sigma score(u, s) / s with the
+ * wrapped-Gaussian score of mdx_wrapped_gaussian_sigma_normalized_score (kmax in [0, 64]), rounded once to f32.
+ * sigmas f32 [batch], one per structure.  A sigma that is not finite and positive, or a coordinate that is not finite, gives
+ * that structure NaNs and MDX_STATUS_ANALYTICAL_SIGMA / _COORDINATES in status (nullable). */
+MDX_API int mdx_equivariant_analytical_score(const float* relative_coordinates, const float* sigmas,
+                                             const float* equilibrium_relative_coordinates, const float* point_group_operations,
+                                             int number_of_operations, double sigma_d_square, int kmax, int64_t batch,
+                                             int number_of_atoms, int spatial_dimension, float* sigma_normalized_scores,
+                                             uint32_t* status, mdx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Fused score network: the reference's MLPScoreNetwork (models/score_networks/mlp_score_network.py:54-370,
