@@ -24,6 +24,7 @@ EXCISE_RADIUS, EXCISE_NEIGHBOURS, EXCISE_MAX_ATOMS = 0, 1, 4096
 STATUS_RANDOM_FILL_COUNT, STATUS_RANDOM_FILL_ENVIRONMENT = 4096, 8192     # mdx_random_fill_environments
 RANDOM_FILL_MAX_ATOMS, RANDOM_FILL_MAX_VOXELS = 1024, 4096
 STATUS_LAP_COST = 16384     # mdx_linear_assignment
+STATUS_TRANSLATION_NO_CANDIDATE = 32768     # mdx_optimal_translation
 TRANSPORT_MAX_ATOMS, TRANSPORT_MAX_OPERATIONS = 256, 48
 EGNN_COORD_NORMALIZE, EGNN_COORD_TANH = 1, 2      # MDX_EGNN_COORD_* (coord_flags of mdx_egnn_node_gather / _coord_aggregate)
 EGNN_CHAIN_MAX_LAYERS = 16
@@ -51,6 +52,7 @@ ABI_SYMBOLS = (
     "mdx_repaint_rows_per_sample", "mdx_excise_environments", "mdx_edit_keep_mask",
     "mdx_random_fill_proposals", "mdx_random_fill_environments",
     "mdx_linear_assignment", "mdx_transport_align", "mdx_equivariant_analytical_score",
+    "mdx_optimal_translation",
 )
 MLP_MAX_HIDDEN = 8
 # options of mdx_mlp_pc_sample (include/mdx_hip.h)
@@ -226,6 +228,8 @@ def _declare(L):
     L.mdx_transport_align.argtypes = [vp, vp, i64, vp, i32, i64, i32, i32, vp, vp, vp, vp, vp, vp]
     L.mdx_equivariant_analytical_score.restype = i32
     L.mdx_equivariant_analytical_score.argtypes = [vp, vp, vp, vp, i32, f64, i32, i64, i32, i32, vp, vp, vp]
+    L.mdx_optimal_translation.restype = i32
+    L.mdx_optimal_translation.argtypes = [vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, vp]
     L.mdx_mlp_forward.restype = i32
     L.mdx_mlp_forward.argtypes = [C.POINTER(Mlp), vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
     L.mdx_mlp_pc_sample.restype = i32

@@ -769,6 +769,37 @@ def equivariant_analytical_score(relative_coordinates, sigmas, equilibrium_relat
 
 
 # ----------------------------------------------------------------------------------------------------------------
+# optimal torus translation (csrc/mdx_optimal_translation.hip)
+# ----------------------------------------------------------------------------------------------------------------
+def optimal_translation(x, y, with_details: bool = False, status: Optional[torch.Tensor] = None):
+    """The reference's find_squared_geodesic_distance_minimizing_translation in one launch (mdx_optimal_translation): x f32 [N, D]
+    (shared by the batch) or [B, N, D]; y f32 [B, N, D].  Returns tau f32 [B, D], the translation in [-1/2, 1/2) that minimises
+    D^2(x, y + tau) per structure and dimension, and with `with_details` also (squared_distance f64 [B, D], number_of_candidates
+    int32 [B, D]).  No host read: an entry whose minimum sits on the boundary holds +inf (as the reference's does) and
+    STATUS_TRANSLATION_NO_CANDIDATE is OR-ed into `status`; a structure with a non-finite coordinate holds NaN (count -1) and
+    STATUS_ANALYTICAL_COORDINATES."""
+    _device_only("the optimal translation", x=x, y=y, status=status)
+    if y.dim() != 3:
+        raise ValueError(f"y has shape {tuple(y.shape)}, expected [B, N, D]")
+    B, N, D = y.shape
+    if x.shape == (N, D):
+        stride = 0
+    elif x.shape == (B, N, D):
+        stride = N * D
+    else:
+        raise ValueError(f"x has shape {tuple(x.shape)}, expected {(N, D)} or {(B, N, D)}")
+    dev = y.device
+    tau = torch.empty(B, D, dtype=F32, device=dev)
+    squared_distance = torch.empty(B, D, dtype=F64, device=dev) if with_details else None
+    number_of_candidates = torch.empty(B, D, dtype=I32, device=dev) if with_details else None
+    check(lib().mdx_optimal_translation(ptr(x, F32, "x"), stride, ptr(y, F32, "y"), B, N, D, ptr(tau, F32, "tau"),
+                                        ptr(squared_distance, F64, "squared_distance"),
+                                        ptr(number_of_candidates, I32, "number_of_candidates"), ptr(status, I32, "status"),
+                                        stream_handle()), "mdx_optimal_translation")
+    return (tau, squared_distance, number_of_candidates) if with_details else tau
+
+
+# ----------------------------------------------------------------------------------------------------------------
 # fused MLP score network
 # ----------------------------------------------------------------------------------------------------------------
 class MlpPack:

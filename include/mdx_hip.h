@@ -68,6 +68,8 @@ extern "C" {
                                             environment's active atom is not one of its constrained atoms; zero likewise  */
 #define MDX_STATUS_LAP_COST 16384u       /* mdx_linear_assignment: a cost that is not finite (|c| >= 1e300 included); that
                                             problem's col_idx is -1 and its cost NaN                                        */
+#define MDX_STATUS_TRANSLATION_NO_CANDIDATE 32768u /* mdx_optimal_translation: no plateau holds its own solution (the minimum sits
+                                            on the boundary tau = +-1/2); that entry's tau and squared distance are +inf   */
 
 #define MDX_MAX_CLASSES 8      /* C supported by the fused atom-type kernels */
 #define MDX_PREDICTOR 0
@@ -543,6 +545,25 @@ MDX_API int mdx_transport_align(const float* x, const float* mu, int64_t mu_batc
                                 int number_of_operations, int64_t batch, int number_of_atoms, int spatial_dimension,
                                 float* aligned_mu, int32_t* operation_idx, int32_t* col_idx, double* costs, uint32_t* status,
                                 mdx_stream_t stream);
+
+/* find_squared_geodesic_distance_minimizing_translation (transport/optimal_translation.py:188-251; csrc/
+ * mdx_optimal_translation.hip): per structure and dimension the translation tau in [-1/2, 1/2) that minimises the squared
+ * geodesic distance D^2(x, y + tau), one workgroup per (structure, dimension), one launch, no host read.  x f32 [N, D] shared by
+ * the batch (x_batch_stride 0) or [batch, N, D] (x_batch_stride N D; anything else is MDX_ERR_INVALID_ARG); y f32 [batch, N, D].
+ * N <= 256 and D <= 3, else MDX_ERR_UNSUPPORTED.  Any finite coordinate is accepted.  Binary64 from the promoted inputs:
+ *   delta_i = y_i - x_i; l0_i = floor((delta_i - 1/2) + 1/2); crossing c_i = -((delta_i - l0_i) - 1/2), sorted ascending
+ *   plateau k = 0 .. N: left_k = -1/2 or c_(k), right_k = c_(k+1) or 1/2, L_k = sum_i l0_i + #{j <= k : c_(j) < 1/2},
+ *   rhs_k = L_k / N - (sum_i delta_i) / N (sums in atom order); a candidate when left_k < rhs_k < right_k, both strict
+ *   cost_k = sum_i g_i^2, g = d - rint(d), d = (y_i + rhs_k) - x_i
+ * tau f32 [batch, D]: rhs_k of the first minimum of the costs in plateau order, rounded once.  Optional outputs (NULL: not
+ * written): squared_distance f64 [batch, D], that minimum; number_of_candidates int32 [batch, D].  An entry without a candidate
+ * gets tau = squared_distance = +inf, the count 0 and MDX_STATUS_TRANSLATION_NO_CANDIDATE in status (nullable), where the
+ * reference has +inf too.  A structure with a coordinate that is not finite gets NaN, the count -1 and
+ * MDX_STATUS_ANALYTICAL_COORDINATES.  No atomics in the arithmetic, every sum in a fixed order, every loop bounded by N + 1
+ * whatever the data: the same bits on every launch and hipGraph replay. */
+MDX_API int mdx_optimal_translation(const float* x, int64_t x_batch_stride, const float* y, int64_t batch, int number_of_atoms,
+                                    int spatial_dimension, float* tau, double* squared_distance, int32_t* number_of_candidates,
+                                    uint32_t* status, mdx_stream_t stream);
 
 /* The equivariant analytical score network's forward (models/score_networks/equivariant_analytical_score_network.py,
  * get_normalized_scores): the alignment above of the shared equilibrium sites [N, D] onto each structure, then per element
