@@ -1,7 +1,8 @@
 """Tensor-level wrappers of the C ABI (include/mdx_hip.h).
 
-Each function validates shapes/dtypes, passes raw device pointers + torch's current HIP stream to the shared
-library, and returns torch tensors that PyTorch owns.  Nothing here computes on the CPU.
+Each function validates shapes, hands its tensors to the shared library through `_hip.call` -- which checks device, dtype
+and contiguity of each against the header's parameter, appends torch's current HIP stream and raises on a non-zero status --
+and returns torch tensors that PyTorch owns.  Nothing here computes on the CPU.
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -10,7 +11,7 @@ from typing import Optional
 import torch
 
 from . import _hip
-from ._hip import Mlp, PcFlags, Rng, Schedule, check, lib, ptr, stream_handle
+from ._hip import Mlp, PcFlags, Rng, Schedule, call, lib
 
 F32, F64, I64, I32 = torch.float32, torch.float64, torch.int64, torch.int32
 
@@ -61,10 +62,8 @@ def noise_schedule_build(total_time_steps: int, schedule_type: str, time_delta: 
     with torch.cuda.device(device):
         vec = [torch.empty(T, dtype=F32, device=device) for _ in range(9)]
         mats = [torch.empty(T, Cn, Cn, dtype=F32, device=device) for _ in range(3)]
-        rc = lib().mdx_noise_schedule_build(T, st, float(time_delta), float(sigma_min), float(sigma_max),
-                                            float(corrector_step_epsilon), Cn,
-                                            *[C.c_void_p(t.data_ptr()) for t in vec + mats], stream_handle())
-    check(rc, "mdx_noise_schedule_build")
+        call("mdx_noise_schedule_build", T, st, float(time_delta), float(sigma_min), float(sigma_max),
+             float(corrector_step_epsilon), Cn, *vec, *mats)
     time, sigma, sigma2, g, g2, eps, s2e, beta, ab = vec
     q, qb, qbm = mats
     return DeviceSchedule(T, Cn, float(sigma_min), time, sigma, sigma2, g, g2, eps, s2e, beta, ab, q, qb, qbm)
@@ -74,21 +73,18 @@ def noise_schedule_build(total_time_steps: int, schedule_type: str, time_delta: 
 # step index / network inputs
 # ----------------------------------------------------------------------------------------------------------------
 def index_set(d_index: torch.Tensor, value: int):
-    check(lib().mdx_index_set(ptr(d_index, I32, "d_index"), int(value), stream_handle()), "mdx_index_set")
+    call("mdx_index_set", d_index, int(value))
 
 
 def index_add(d_index: torch.Tensor, delta: int):
-    check(lib().mdx_index_add(ptr(d_index, I32, "d_index"), int(delta), stream_handle()), "mdx_index_add")
+    call("mdx_index_add", d_index, int(delta))
 
 
 def fill_time_sigma(sched: DeviceSchedule, mode: int, index_i: int, d_index: Optional[torch.Tensor],
                     time_out: torch.Tensor, sigma_out: torch.Tensor):
     batch = time_out.numel()
     assert sigma_out.numel() == batch
-    rc = lib().mdx_fill_time_sigma(C.byref(sched.c_struct), mode, int(index_i), ptr(d_index, I32, "d_index"),
-                                   ptr(time_out, F32, "time_out"), ptr(sigma_out, F32, "sigma_out"), batch,
-                                   stream_handle())
-    check(rc, "mdx_fill_time_sigma")
+    call("mdx_fill_time_sigma", C.byref(sched.c_struct), mode, int(index_i), d_index, time_out, sigma_out, batch)
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -101,15 +97,9 @@ def relative_coordinates_update(x, s, z, score_weight=None, gaussian_noise_weigh
     out = torch.empty_like(x) if out is None else out
     if weights is not None:
         assert weights.numel() == 3
-        rc = lib().mdx_relative_coordinates_update_dev(ptr(x, F32, "x"), ptr(s, F32, "sigma_normalized_scores"), ptr(z, F32, "z"),
-                                                       ptr(weights, F32, "weights"), x.numel(), ptr(out, F32, "out"),
-                                                       stream_handle())
-        check(rc, "mdx_relative_coordinates_update_dev")
+        call("mdx_relative_coordinates_update_dev", x, s, z, weights, x.numel(), out)
         return out
-    rc = lib().mdx_relative_coordinates_update(ptr(x, F32, "x"), ptr(s, F32, "sigma_normalized_scores"),
-                                               ptr(z, F32, "z"), float(score_weight), float(gaussian_noise_weight),
-                                               float(sigma), x.numel(), ptr(out, F32, "out"), stream_handle())
-    check(rc, "mdx_relative_coordinates_update")
+    call("mdx_relative_coordinates_update", x, s, z, float(score_weight), float(gaussian_noise_weight), float(sigma), x.numel(), out)
     return out
 
 
@@ -119,15 +109,9 @@ def lattice_parameters_update(l, s, z, score_weight=None, gaussian_noise_weight=
     out = torch.empty_like(l) if out is None else out
     if weights is not None:
         assert weights.numel() == 3
-        rc = lib().mdx_lattice_parameters_update_dev(ptr(l, F32, "l"), ptr(s, F32, "sigma_normalized_scores"), ptr(z, F32, "z"),
-                                                     ptr(weights, F32, "weights"), l.numel(), ptr(out, F32, "out"),
-                                                     stream_handle())
-        check(rc, "mdx_lattice_parameters_update_dev")
+        call("mdx_lattice_parameters_update_dev", l, s, z, weights, l.numel(), out)
         return out
-    rc = lib().mdx_lattice_parameters_update(ptr(l, F32, "l"), ptr(s, F32, "sigma_normalized_scores"),
-                                             ptr(z, F32, "z"), float(score_weight), float(gaussian_noise_weight),
-                                             float(sigma_n), l.numel(), ptr(out, F32, "out"), stream_handle())
-    check(rc, "mdx_lattice_parameters_update")
+    call("mdx_lattice_parameters_update", l, s, z, float(score_weight), float(gaussian_noise_weight), float(sigma_n), l.numel(), out)
     return out
 
 
@@ -138,12 +122,8 @@ def atom_types_update(logits, atom_types, q, q_bar, q_bar_tm1, gumbel, u, small_
     assert q.shape == q_bar.shape == q_bar_tm1.shape == (Cn, Cn)
     out = torch.empty_like(atom_types)
     p_out = torch.empty_like(logits) if return_probabilities else None
-    rc = lib().mdx_atom_types_update(ptr(logits, F32, "logits"), ptr(atom_types, I64, "atom_types"),
-                                     ptr(q, F32, "q"), ptr(q_bar, F32, "q_bar"), ptr(q_bar_tm1, F32, "q_bar_tm1"),
-                                     ptr(gumbel, F32, "gumbel"), ptr(u, F32, "u"), B, N, Cn, float(small_epsilon),
-                                     int(bool(greedy)), int(bool(one_transition)), ptr(out, I64, "out"),
-                                     ptr(p_out, F32, "p_out"), stream_handle())
-    check(rc, "mdx_atom_types_update")
+    call("mdx_atom_types_update", logits, atom_types, q, q_bar, q_bar_tm1, gumbel, u, B, N, Cn, float(small_epsilon),
+         int(bool(greedy)), int(bool(one_transition)), out, p_out)
     return (out, p_out) if return_probabilities else out
 
 
@@ -154,14 +134,8 @@ def pc_step_update(sched: DeviceSchedule, mode: int, index_i: int, d_index: Opti
                    atom_types, x, l, logits, score_x, score_l, z_coordinates, gumbel, u, z_lattice, rng: Rng,
                    atom_types_out, x_out, l_out, status: Optional[torch.Tensor]):
     B, N, d = x.shape
-    rc = lib().mdx_pc_step_update(
-        C.byref(sched.c_struct), int(mode), int(index_i), ptr(d_index, I32, "d_index"), C.byref(flags),
-        ptr(atom_types, I64, "atom_types"), ptr(x, F32, "x"), ptr(l, F32, "l"), ptr(logits, F32, "logits"),
-        ptr(score_x, F32, "score_x"), ptr(score_l, F32, "score_l"), ptr(z_coordinates, F32, "z_coordinates"),
-        ptr(gumbel, F32, "gumbel"), ptr(u, F32, "u"), ptr(z_lattice, F32, "z_lattice"), rng, B, N, d,
-        ptr(atom_types_out, I64, "atom_types_out"), ptr(x_out, F32, "x_out"), ptr(l_out, F32, "l_out"),
-        ptr(status, I32, "status"), stream_handle())
-    check(rc, "mdx_pc_step_update")
+    call("mdx_pc_step_update", C.byref(sched.c_struct), int(mode), int(index_i), d_index, C.byref(flags), atom_types, x, l,
+         logits, score_x, score_l, z_coordinates, gumbel, u, z_lattice, rng, B, N, d, atom_types_out, x_out, l_out, status)
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -175,13 +149,9 @@ def adaptive_corrector_statistics(sched: DeviceSchedule, index_i: int, d_index: 
     A None z is regenerated in registers from `rng`."""
     B, N, d = score_x.shape
     assert workspace.numel() == 4 * B and totals.numel() == 8 and (weights is None or weights.numel() == 6)
-    rc = lib().mdx_adaptive_corrector_statistics(
-        C.byref(sched.c_struct), int(index_i), ptr(d_index, I32, "d_index"), ptr(score_x, F32, "score_x"),
-        ptr(score_l, F32, "score_l"), ptr(z_coordinates, F32, "z_coordinates"),
-        ptr(z_lattice_for_step_size, F32, "z_lattice_for_step_size"), rng, B, N, d, int(bool(use_fixed_lattice_parameters)),
-        float(corrector_r), float(small_epsilon), ptr(workspace, F32, "workspace"), ptr(totals, F64, "totals"),
-        ptr(weights, F32, "weights"), stream_handle())
-    check(rc, "mdx_adaptive_corrector_statistics")
+    call("mdx_adaptive_corrector_statistics", C.byref(sched.c_struct), int(index_i), d_index, score_x, score_l, z_coordinates,
+         z_lattice_for_step_size, rng, B, N, d, int(bool(use_fixed_lattice_parameters)), float(corrector_r),
+         float(small_epsilon), workspace, totals, weights)
 
 
 def adaptive_corrector_step_size(sched: DeviceSchedule, index_i: int, d_index: Optional[torch.Tensor], totals,
@@ -190,11 +160,8 @@ def adaptive_corrector_step_size(sched: DeviceSchedule, index_i: int, d_index: O
     """Stage 2 (mdx_adaptive_corrector_step_size): weights float32 [6] = {eps, sqrt(2 eps), sigma, eps_L, sqrt(2 eps_L),
     sigma_n} from totals float64 [8] (all-reduced by the caller when the batch is sharded)."""
     assert totals.numel() == 8 and weights.numel() == 6
-    rc = lib().mdx_adaptive_corrector_step_size(
-        C.byref(sched.c_struct), int(index_i), ptr(d_index, I32, "d_index"), ptr(totals, F64, "totals"), int(number_of_atoms),
-        int(spatial_dimension), int(bool(use_fixed_lattice_parameters)), float(corrector_r), float(small_epsilon),
-        ptr(weights, F32, "weights"), stream_handle())
-    check(rc, "mdx_adaptive_corrector_step_size")
+    call("mdx_adaptive_corrector_step_size", C.byref(sched.c_struct), int(index_i), d_index, totals, int(number_of_atoms),
+         int(spatial_dimension), int(bool(use_fixed_lattice_parameters)), float(corrector_r), float(small_epsilon), weights)
 
 
 def adaptive_corrector_update(sched: DeviceSchedule, mode: int, index_i: int, d_index: Optional[torch.Tensor], flags: PcFlags,
@@ -203,14 +170,9 @@ def adaptive_corrector_update(sched: DeviceSchedule, mode: int, index_i: int, d_
     """Stage 3 (mdx_adaptive_corrector_update): pc_step_update's operands; corrector: scalars from `weights`; predictor: atom
     types only."""
     B, N, d = x.shape
-    rc = lib().mdx_adaptive_corrector_update(
-        C.byref(sched.c_struct), int(mode), int(index_i), ptr(d_index, I32, "d_index"), C.byref(flags),
-        ptr(atom_types, I64, "atom_types"), ptr(x, F32, "x"), ptr(l, F32, "l"), ptr(logits, F32, "logits"),
-        ptr(score_x, F32, "score_x"), ptr(score_l, F32, "score_l"), ptr(z_coordinates, F32, "z_coordinates"),
-        ptr(gumbel, F32, "gumbel"), ptr(u, F32, "u"), ptr(z_lattice, F32, "z_lattice"), ptr(weights, F32, "weights"), rng,
-        B, N, d, ptr(atom_types_out, I64, "atom_types_out"), ptr(x_out, F32, "x_out"), ptr(l_out, F32, "l_out"),
-        ptr(status, I32, "status"), stream_handle())
-    check(rc, "mdx_adaptive_corrector_update")
+    call("mdx_adaptive_corrector_update", C.byref(sched.c_struct), int(mode), int(index_i), d_index, C.byref(flags), atom_types,
+         x, l, logits, score_x, score_l, z_coordinates, gumbel, u, z_lattice, weights, rng, B, N, d, atom_types_out, x_out, l_out,
+         status)
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -222,13 +184,9 @@ def noise_relative_coordinates(x0, z, sigma, out=None):
     out = torch.empty_like(x0) if out is None else out
     if isinstance(sigma, torch.Tensor):
         assert sigma.shape == x0.shape, "sigmas array is expected to be of the same shape as the real_relative_coordinates array"
-        rc = lib().mdx_noise_relative_coordinates_sigmas(ptr(x0, F32, "x0"), ptr(z, F32, "z"), ptr(sigma, F32, "sigmas"),
-                                                         x0.numel(), ptr(out, F32, "out"), stream_handle())
-        check(rc, "mdx_noise_relative_coordinates_sigmas")
+        call("mdx_noise_relative_coordinates_sigmas", x0, z, sigma, x0.numel(), out)
         return out
-    rc = lib().mdx_noise_relative_coordinates(ptr(x0, F32, "x0"), ptr(z, F32, "z"), float(sigma), x0.numel(),
-                                              ptr(out, F32, "out"), stream_handle())
-    check(rc, "mdx_noise_relative_coordinates")
+    call("mdx_noise_relative_coordinates", x0, z, float(sigma), x0.numel(), out)
     return out
 
 
@@ -236,9 +194,7 @@ def noise_lattice_parameters(l0, z, sigmas_n):
     """sigmas_n * z + l0, element by element (mdx_noise_lattice_parameters)."""
     assert l0.shape == z.shape == sigmas_n.shape
     out = torch.empty_like(l0)
-    rc = lib().mdx_noise_lattice_parameters(ptr(l0, F32, "l0"), ptr(z, F32, "z"), ptr(sigmas_n, F32, "sigmas_n"), l0.numel(),
-                                            ptr(out, F32, "out"), stream_handle())
-    check(rc, "mdx_noise_lattice_parameters")
+    call("mdx_noise_lattice_parameters", l0, z, sigmas_n, l0.numel(), out)
     return out
 
 
@@ -249,14 +205,10 @@ def noise_atom_types(a0, q_bar, u):
     out = torch.empty_like(a0)
     if q_bar.dim() > 2:
         assert q_bar.shape == tuple(a0.shape) + (Cn, Cn), "q_bar array first dimensions should match real_atom_types array"
-        rc = lib().mdx_noise_atom_types_per_atom(ptr(a0, I64, "a0"), ptr(q_bar, F32, "q_bar"), ptr(u, F32, "u"), a0.numel(),
-                                                 Cn, ptr(out, I64, "out"), stream_handle())
-        check(rc, "mdx_noise_atom_types_per_atom")
+        call("mdx_noise_atom_types_per_atom", a0, q_bar, u, a0.numel(), Cn, out)
         return out
     assert q_bar.shape == (Cn, Cn)
-    rc = lib().mdx_noise_atom_types(ptr(a0, I64, "a0"), ptr(q_bar, F32, "q_bar"), ptr(u, F32, "u"), a0.numel(), Cn,
-                                    ptr(out, I64, "out"), stream_handle())
-    check(rc, "mdx_noise_atom_types")
+    call("mdx_noise_atom_types", a0, q_bar, u, a0.numel(), Cn, out)
     return out
 
 
@@ -264,21 +216,14 @@ def repaint_constrained_rows(sched: DeviceSchedule, index_i: int, d_index, const
                              constrained_indices, z, u, rng: Rng, x_inout, a_inout):
     B, N, d = x_inout.shape
     K = constrained_x.shape[0]
-    rc = lib().mdx_repaint_constrained_rows(
-        C.byref(sched.c_struct), int(index_i), ptr(d_index, I32, "d_index"), ptr(constrained_x, F32, "constrained_x"),
-        ptr(constrained_a, I64, "constrained_a"), ptr(constrained_indices, I64, "constrained_indices"), K,
-        ptr(z, F32, "z"), ptr(u, F32, "u"), rng, B, N, d, ptr(x_inout, F32, "x"), ptr(a_inout, I64, "a"),
-        stream_handle())
-    check(rc, "mdx_repaint_constrained_rows")
+    call("mdx_repaint_constrained_rows", C.byref(sched.c_struct), int(index_i), d_index, constrained_x, constrained_a,
+         constrained_indices, K, z, u, rng, B, N, d, x_inout, a_inout)
 
 
 def forward_diffusion_step(sched: DeviceSchedule, index_i: int, d_index, z, u, rng: Rng, x_inout, a_inout):
     """RePaint resampling: one forward-process step i -> i+1 on every atom, in place (mdx_forward_diffusion_step)."""
     B, N, d = x_inout.shape
-    rc = lib().mdx_forward_diffusion_step(C.byref(sched.c_struct), int(index_i), ptr(d_index, I32, "d_index"),
-                                          ptr(z, F32, "z"), ptr(u, F32, "u"), rng, B, N, d, ptr(x_inout, F32, "x"),
-                                          ptr(a_inout, I64, "a"), stream_handle())
-    check(rc, "mdx_forward_diffusion_step")
+    call("mdx_forward_diffusion_step", C.byref(sched.c_struct), int(index_i), d_index, z, u, rng, B, N, d, x_inout, a_inout)
 
 
 def repaint_rows_per_sample(sched: DeviceSchedule, index_i: int, d_index, constrained_x, constrained_a, constrained_indices,
@@ -290,12 +235,8 @@ def repaint_rows_per_sample(sched: DeviceSchedule, index_i: int, d_index, constr
     E, K = constrained_a.shape
     assert constrained_x.shape == (E, K, d) and constrained_indices.shape == (E, K) and counts.shape == (E,)
     assert sample_environment.shape == (B,) and a_inout.shape == (B, N)
-    rc = lib().mdx_repaint_rows_per_sample(
-        C.byref(sched.c_struct), int(index_i), ptr(d_index, I32, "d_index"), ptr(constrained_x, F32, "constrained_x"),
-        ptr(constrained_a, I64, "constrained_a"), ptr(constrained_indices, I64, "constrained_indices"),
-        ptr(counts, I32, "counts"), E, K, ptr(sample_environment, I32, "sample_environment"), ptr(z, F32, "z"),
-        ptr(u, F32, "u"), rng, B, N, d, ptr(x_inout, F32, "x"), ptr(a_inout, I64, "a"), stream_handle())
-    check(rc, "mdx_repaint_rows_per_sample")
+    call("mdx_repaint_rows_per_sample", C.byref(sched.c_struct), int(index_i), d_index, constrained_x, constrained_a,
+         constrained_indices, counts, E, K, sample_environment, z, u, rng, B, N, d, x_inout, a_inout)
 
 
 class ExcisionCapacityError(_hip.MdxError):
@@ -336,12 +277,8 @@ def excise_environments(relative_coordinates, box_sides, central_atoms, radial_c
     if own:
         status = torch.zeros(1, dtype=I32, device=dev)
     mode = _hip.EXCISE_RADIUS if number_of_neighbors is None else _hip.EXCISE_NEIGHBOURS
-    check(lib().mdx_excise_environments(
-        ptr(relative_coordinates, F64, "relative_coordinates"), ptr(box_sides, F64, "box_sides"), N, d,
-        ptr(central_atoms, I64, "central_atoms"), E, mode, float(radial_cutoff or 0.0), int(number_of_neighbors or 0),
-        int(bool(center_atoms)), ptr(new_box_sides, F64, "new_box_sides"), cap, ptr(source, I64, "source_indices"),
-        ptr(cx, F32, "constrained_x"), ptr(counts, I32, "counts"), ptr(status, I32, "status"), stream_handle()),
-        "mdx_excise_environments")
+    call("mdx_excise_environments", relative_coordinates, box_sides, N, d, central_atoms, E, mode, float(radial_cutoff or 0.0),
+         int(number_of_neighbors or 0), int(bool(center_atoms)), new_box_sides, cap, source, cx, counts, status)
     if own:
         word = int(status.item())
         if word & _hip.STATUS_EXCISE_CENTRAL_INDEX:
@@ -361,11 +298,8 @@ def edit_keep_mask(relative_coordinates, lattice_parameters, sample_environment,
     assert lattice_parameters.dim() == 2 and lattice_parameters.shape[0] == B and lattice_parameters.shape[1] >= d
     assert sample_environment.shape == (B,) and active_atoms.shape == counts.shape and active_atoms.dim() == 1
     keep = torch.empty(B, N, dtype=torch.uint8, device=relative_coordinates.device)
-    check(lib().mdx_edit_keep_mask(ptr(relative_coordinates, F32, "relative_coordinates"),
-                                   ptr(lattice_parameters, F32, "lattice_parameters"), lattice_parameters.shape[1],
-                                   ptr(sample_environment, I32, "sample_environment"), ptr(active_atoms, I32, "active_atoms"),
-                                   ptr(counts, I32, "counts"), counts.shape[0], float(radius), B, N, d, ptr(keep, torch.uint8, "keep"),
-                                   stream_handle()), "mdx_edit_keep_mask")
+    call("mdx_edit_keep_mask", relative_coordinates, lattice_parameters, lattice_parameters.shape[1], sample_environment,
+         active_atoms, counts, counts.shape[0], float(radius), B, N, d, keep)
     return keep
 
 
@@ -386,10 +320,8 @@ def random_fill_proposals(seed: int, call: int, first_sample: int, batch: int, m
         uniforms = torch.empty(B, M, N, d, dtype=F64, device=device)
         types = torch.empty(B, M, N, dtype=I32, device=device)
         voxels = torch.empty(B, M, N, dtype=I32, device=device) if number_of_voxels else None
-        check(lib().mdx_random_fill_proposals(int(seed) & 0xFFFFFFFFFFFFFFFF, int(call), int(first_sample), B, M, N, d,
-                                              int(num_atom_types), int(number_of_voxels), ptr(uniforms, F64, "uniforms"),
-                                              ptr(types, I32, "types"), ptr(voxels, I32, "voxels"), stream_handle()),
-              "mdx_random_fill_proposals")
+        _hip.call("mdx_random_fill_proposals", int(seed) & 0xFFFFFFFFFFFFFFFF, int(call), int(first_sample), B, M, N, d,
+                  int(num_atom_types), int(number_of_voxels), uniforms, types, voxels)
     return uniforms, types, voxels
 
 
@@ -426,13 +358,9 @@ def random_fill_environments(uniforms, types, voxels, partition, constrained_x, 
     own = status is None
     if own:
         status = torch.zeros(1, dtype=I32, device=dev)
-    check(lib().mdx_random_fill_environments(
-        ptr(uniforms, F64, "uniforms"), ptr(types, I32, "types"), ptr(voxels, I32, "voxels"), words,
-        ptr(constrained_x, F64, "constrained_x"), ptr(constrained_a, I64, "constrained_a"), ptr(counts, I32, "counts"),
-        ptr(active, I32, "active"), E, K, ptr(sample_environment, I32, "sample_environment"), ptr(box_sides, F64, "box_sides"),
-        M, float(minimal_interatomic_distance), B, N, d, ptr(x, F64, "x"), ptr(a, I64, "a"), ptr(active_out, I32, "active_out"),
-        ptr(attempts, I32, "attempts"), ptr(accepted, torch.uint8, "accepted"), ptr(min_distance, F64, "min_distance"),
-        ptr(status, I32, "status"), stream_handle()), "mdx_random_fill_environments")
+    call("mdx_random_fill_environments", uniforms, types, voxels, words, constrained_x, constrained_a, counts, active, E, K,
+         sample_environment, box_sides, M, float(minimal_interatomic_distance), B, N, d, x, a, active_out, attempts, accepted,
+         min_distance, status)
     if own:
         word = int(status.item())
         if word & _hip.STATUS_RANDOM_FILL_COUNT:
@@ -455,12 +383,8 @@ def radius_graph(cartesian_positions, basis_vectors, radial_cutoff: float, uniqu
     assert d == 3 and basis_vectors.shape == (B, 3, 3)
     dev = cartesian_positions.device
     counts = torch.empty(B, N, dtype=I64, device=dev)
-    L = lib()
-    rc = L.mdx_radius_graph_count(ptr(cartesian_positions, F32, "cartesian_positions"),
-                                  ptr(basis_vectors, F32, "basis_vectors"), float(radial_cutoff), B, N,
-                                  int(bool(unique)), ptr(counts, I64, "counts"), ptr(status, I32, "status"),
-                                  stream_handle())
-    check(rc, "mdx_radius_graph_count")
+    call("mdx_radius_graph_count", cartesian_positions, basis_vectors, float(radial_cutoff), B, N, int(bool(unique)), counts,
+         status)
     inclusive = torch.cumsum(counts.view(-1), 0)
     offsets = inclusive - counts.view(-1)
     E = int(inclusive[-1].item()) if B * N > 0 else 0
@@ -468,11 +392,8 @@ def radius_graph(cartesian_positions, basis_vectors, radial_cutoff: float, uniqu
     image = None if unique else torch.empty(E, dtype=I32, device=dev)
     shifts = None if (unique or not want_shifts) else torch.empty(E, 3, dtype=F32, device=dev)
     if E > 0:
-        rc = L.mdx_radius_graph_fill(ptr(cartesian_positions, F32, "cartesian_positions"),
-                                     ptr(basis_vectors, F32, "basis_vectors"), float(radial_cutoff), B, N,
-                                     int(bool(unique)), ptr(offsets, I64, "offsets"), ptr(edges, I64, "edges"),
-                                     ptr(image, I32, "image"), ptr(shifts, F32, "shifts"), stream_handle())
-        check(rc, "mdx_radius_graph_fill")
+        call("mdx_radius_graph_fill", cartesian_positions, basis_vectors, float(radial_cutoff), B, N, int(bool(unique)),
+             offsets, edges, image, shifts)
     return dict(counts=counts, edges=edges, image=image, shifts=shifts)
 
 
@@ -485,18 +406,12 @@ def radius_graph_static(cartesian_positions, basis_vectors, radial_cutoff: float
     assert d == 3 and basis_vectors.shape == (B, 3, 3)
     dev = cartesian_positions.device
     counts = torch.empty(B * N, dtype=I64, device=dev)
-    L = lib()
-    check(L.mdx_radius_graph_count(ptr(cartesian_positions, F32, "cartesian_positions"),
-                                   ptr(basis_vectors, F32, "basis_vectors"), float(radial_cutoff), B, N, 1,
-                                   ptr(counts, I64, "counts"), ptr(status, I32, "status"), stream_handle()),
-          "mdx_radius_graph_count")
+    call("mdx_radius_graph_count", cartesian_positions, basis_vectors, float(radial_cutoff), B, N, 1, counts, status)
     inclusive = torch.cumsum(counts, 0)
     offsets = inclusive - counts
     edges = torch.empty(int(capacity), 2, dtype=I64, device=dev)
-    check(L.mdx_radius_graph_fill_capped(ptr(cartesian_positions, F32, "cartesian_positions"),
-                                         ptr(basis_vectors, F32, "basis_vectors"), float(radial_cutoff), B, N, 1,
-                                         ptr(offsets, I64, "offsets"), int(capacity), ptr(edges, I64, "edges"), None, None,
-                                         ptr(status, I32, "status"), stream_handle()), "mdx_radius_graph_fill_capped")
+    call("mdx_radius_graph_fill_capped", cartesian_positions, basis_vectors, float(radial_cutoff), B, N, 1, offsets,
+         int(capacity), edges, None, None, status)
     return dict(counts=counts, offsets=offsets, edges=edges, n_edges=inclusive[-1:])
 
 
@@ -515,12 +430,8 @@ def egnn_radius_graph(relative_coordinates, lattice_parameters, clip_min: float,
     edges = torch.empty(int(capacity), 2, dtype=I64, device=dev)
     words = int(lib().mdx_egnn_radius_graph_workspace_words(B, N)) if two_launches else 0
     workspace = torch.empty(words, dtype=I64, device=dev) if words else None
-    check(lib().mdx_egnn_radius_graph(ptr(relative_coordinates, F32, "relative_coordinates"),
-                                      ptr(lattice_parameters, F32, "lattice_parameters"), lattice_parameters.shape[1],
-                                      float(clip_min), float(radial_cutoff), B, N, int(capacity), ptr(counts, I64, "counts"),
-                                      ptr(offsets, I64, "offsets"), ptr(n_edges, I64, "n_edges"), ptr(edges, I64, "edges"),
-                                      ptr(status, I32, "status"), ptr(workspace, I64, "workspace"), words, stream_handle()),
-          "mdx_egnn_radius_graph")
+    call("mdx_egnn_radius_graph", relative_coordinates, lattice_parameters, lattice_parameters.shape[1], float(clip_min),
+         float(radial_cutoff), B, N, int(capacity), counts, offsets, n_edges, edges, status, workspace, words)
     return dict(counts=counts, offsets=offsets, edges=edges, n_edges=n_edges)
 
 
@@ -537,11 +448,8 @@ def force_field_pseudo_force(relative_coordinates, lattice_parameters, clip_min:
     if score_in is not None and score_in.shape != relative_coordinates.shape:
         raise ValueError(f"score_in has shape {tuple(score_in.shape)}, expected {tuple(relative_coordinates.shape)}")
     out = torch.empty(B, N, 3, dtype=F32, device=relative_coordinates.device)
-    check(lib().mdx_force_field_pseudo_force(ptr(relative_coordinates, F32, "relative_coordinates"),
-                                             ptr(lattice_parameters, F32, "lattice_parameters"), lattice_parameters.shape[1],
-                                             float(clip_min), float(radial_cutoff), float(2.0 * strength), B, N,
-                                             ptr(score_in, F32, "score_in"), ptr(out, F32, "out"), ptr(status, I32, "status"),
-                                             stream_handle()), "mdx_force_field_pseudo_force")
+    call("mdx_force_field_pseudo_force", relative_coordinates, lattice_parameters, lattice_parameters.shape[1], float(clip_min),
+         float(radial_cutoff), float(2.0 * strength), B, N, score_in, out, status)
     return out
 
 
@@ -582,13 +490,8 @@ def stillinger_weber_energy_forces(relative_coordinates, lattice_parameters, ato
     own_status = status is None
     if own_status:
         status = torch.zeros(1, dtype=I32, device=dev)
-    check(lib().mdx_stillinger_weber_energy_forces(ptr(relative_coordinates, F32, "relative_coordinates"),
-                                                   ptr(lattice_parameters, F32, "lattice_parameters"), lattice_parameters.shape[1],
-                                                   ptr(atom_types, I64, "atom_types"), ptr(parameter_table, F64, "parameter_table"),
-                                                   n, B, N, int(neighbour_capacity), ptr(workspace, F64, "workspace"),
-                                                   workspace.numel(), ptr(energies, F64, "energies"), ptr(forces, F64, "forces"),
-                                                   ptr(status, I32, "status"), stream_handle()),
-          "mdx_stillinger_weber_energy_forces")
+    call("mdx_stillinger_weber_energy_forces", relative_coordinates, lattice_parameters, lattice_parameters.shape[1], atom_types,
+         parameter_table, n, B, N, int(neighbour_capacity), workspace, workspace.numel(), energies, forces, status)
     if own_status:
         bits = int(status.item())
         if bits & _hip.STATUS_SW_ATOM_TYPE:
@@ -639,11 +542,8 @@ def wrapped_gaussian_sigma_normalized_score(relative_coordinates, sigmas, kmax: 
     if relative_coordinates.shape != sigmas.shape:
         raise ValueError("relative_coordinates and sigmas must have the same shape")
     out = torch.empty_like(relative_coordinates)
-    check(lib().mdx_wrapped_gaussian_sigma_normalized_score(ptr(relative_coordinates, F32, "relative_coordinates"),
-                                                            ptr(sigmas, F32, "sigmas"), relative_coordinates.numel(), int(kmax),
-                                                            int(bool(coordinates_bounded)), ptr(out, F32, "out"),
-                                                            ptr(status, I32, "status"), stream_handle()),
-          "mdx_wrapped_gaussian_sigma_normalized_score")
+    call("mdx_wrapped_gaussian_sigma_normalized_score", relative_coordinates, sigmas, relative_coordinates.numel(), int(kmax),
+         int(bool(coordinates_bounded)), out, status)
     return out
 
 
@@ -658,9 +558,7 @@ def log_wrapped_gaussians(relative_coordinates, sigmas, kmax: int, row_length: i
         raise ValueError(f"row_length {row_length} does not divide {relative_coordinates.numel()} elements")
     rows = relative_coordinates.numel() // row_length
     out = torch.empty(rows, dtype=F32, device=relative_coordinates.device)
-    check(lib().mdx_log_wrapped_gaussians(ptr(relative_coordinates, F32, "relative_coordinates"), ptr(sigmas, F32, "sigmas"), rows,
-                                          int(row_length), int(kmax), ptr(out, F32, "out"), ptr(status, I32, "status"),
-                                          stream_handle()), "mdx_log_wrapped_gaussians")
+    call("mdx_log_wrapped_gaussians", relative_coordinates, sigmas, rows, int(row_length), int(kmax), out, status)
     return out
 
 
@@ -683,11 +581,8 @@ def analytical_score(relative_coordinates, sigmas, equilibrium_relative_coordina
     dev = relative_coordinates.device
     scores = torch.empty(B, N, D, dtype=F32, device=dev)
     probabilities = torch.empty(B, dtype=F32, device=dev) if with_probabilities else None
-    check(lib().mdx_analytical_score(ptr(relative_coordinates, F32, "relative_coordinates"), ptr(sigmas, F32, "sigmas"), per_element,
-                                     ptr(equilibrium_relative_coordinates, F32, "equilibrium_relative_coordinates"),
-                                     float(sigma_d_square), int(kmax), int(bool(use_permutation_invariance)), B, N, D,
-                                     ptr(scores, F32, "scores"), ptr(probabilities, F32, "probabilities"),
-                                     ptr(status, I32, "status"), stream_handle()), "mdx_analytical_score")
+    call("mdx_analytical_score", relative_coordinates, sigmas, per_element, equilibrium_relative_coordinates,
+         float(sigma_d_square), int(kmax), int(bool(use_permutation_invariance)), B, N, D, scores, probabilities, status)
     return scores, probabilities
 
 
@@ -709,9 +604,7 @@ def linear_assignment(cost_matrices, status: Optional[torch.Tensor] = None):
     M, n, _ = cost_matrices.shape
     col_idx = torch.empty(M, n, dtype=I32, device=cost_matrices.device)
     costs = torch.empty(M, dtype=F64, device=cost_matrices.device)
-    check(lib().mdx_linear_assignment(ptr(cost_matrices, cost_matrices.dtype, "cost_matrices"), int(cost_matrices.dtype == F64), M, n,
-                                      ptr(col_idx, I32, "col_idx"), ptr(costs, F64, "costs"), ptr(status, I32, "status"),
-                                      stream_handle()), "mdx_linear_assignment")
+    call("mdx_linear_assignment", cost_matrices, int(cost_matrices.dtype == F64), M, n, col_idx, costs, status)
     return col_idx, costs
 
 
@@ -735,11 +628,7 @@ def transport_align(x, mu, point_group_operations, with_details: bool = False, s
     operation_idx = torch.empty(B, dtype=I32, device=dev) if with_details else None
     col_idx = torch.empty(B, N, dtype=I32, device=dev) if with_details else None
     costs = torch.empty(B, O, dtype=F64, device=dev) if with_details else None
-    check(lib().mdx_transport_align(ptr(x, F32, "x"), ptr(mu, F32, "mu"), stride,
-                                    ptr(point_group_operations, F32, "point_group_operations"), O, B, N, D,
-                                    ptr(aligned, F32, "aligned"), ptr(operation_idx, I32, "operation_idx"),
-                                    ptr(col_idx, I32, "col_idx"), ptr(costs, F64, "costs"), ptr(status, I32, "status"),
-                                    stream_handle()), "mdx_transport_align")
+    call("mdx_transport_align", x, mu, stride, point_group_operations, O, B, N, D, aligned, operation_idx, col_idx, costs, status)
     return (aligned, operation_idx, col_idx, costs) if with_details else aligned
 
 
@@ -760,11 +649,8 @@ def equivariant_analytical_score(relative_coordinates, sigmas, equilibrium_relat
     if sigmas.numel() != B:
         raise ValueError(f"sigmas has shape {tuple(sigmas.shape)}: expected one per structure, [{B}]")
     scores = torch.empty(B, N, D, dtype=F32, device=relative_coordinates.device)
-    check(lib().mdx_equivariant_analytical_score(ptr(relative_coordinates, F32, "relative_coordinates"), ptr(sigmas, F32, "sigmas"),
-                                                 ptr(equilibrium_relative_coordinates, F32, "equilibrium_relative_coordinates"),
-                                                 ptr(point_group_operations, F32, "point_group_operations"), O,
-                                                 float(sigma_d_square), int(kmax), B, N, D, ptr(scores, F32, "scores"),
-                                                 ptr(status, I32, "status"), stream_handle()), "mdx_equivariant_analytical_score")
+    call("mdx_equivariant_analytical_score", relative_coordinates, sigmas, equilibrium_relative_coordinates,
+         point_group_operations, O, float(sigma_d_square), int(kmax), B, N, D, scores, status)
     return scores
 
 
@@ -792,10 +678,7 @@ def optimal_translation(x, y, with_details: bool = False, status: Optional[torch
     tau = torch.empty(B, D, dtype=F32, device=dev)
     squared_distance = torch.empty(B, D, dtype=F64, device=dev) if with_details else None
     number_of_candidates = torch.empty(B, D, dtype=I32, device=dev) if with_details else None
-    check(lib().mdx_optimal_translation(ptr(x, F32, "x"), stride, ptr(y, F32, "y"), B, N, D, ptr(tau, F32, "tau"),
-                                        ptr(squared_distance, F64, "squared_distance"),
-                                        ptr(number_of_candidates, I32, "number_of_candidates"), ptr(status, I32, "status"),
-                                        stream_handle()), "mdx_optimal_translation")
+    call("mdx_optimal_translation", x, stride, y, B, N, D, tau, squared_distance, number_of_candidates, status)
     return (tau, squared_distance, number_of_candidates) if with_details else tau
 
 
@@ -863,8 +746,7 @@ class MlpPack:
         if n_floats > 0:      # the kernels' own layout, built once: kernel start-up becomes one coalesced copy
             self.image = torch.empty(n_floats, dtype=F32, device=device)
             with torch.cuda.device(device):
-                check(lib().mdx_mlp_pack_image(C.byref(m), ptr(self.image, F32, "image"), stream_handle()),
-                      "mdx_mlp_pack_image")
+                call("mdx_mlp_pack_image", C.byref(m), self.image)
             m.packed_image = self.image.data_ptr()
         self.c_struct = m
         self.device = torch.device(device)
@@ -960,11 +842,7 @@ def mlp_forward(pack: MlpPack, atom_types, x, l, time, sigma):
     logits = torch.empty(B, N, pack.num_classes, dtype=F32, device=x.device)
     score_x = torch.empty_like(x)
     score_l = torch.empty_like(l)
-    rc = lib().mdx_mlp_forward(C.byref(pack.c_struct), ptr(atom_types, I64, "atom_types"), ptr(x, F32, "x"),
-                               ptr(l, F32, "l"), ptr(time, F32, "time"), ptr(sigma, F32, "sigma"), B,
-                               ptr(logits, F32, "logits"), ptr(score_x, F32, "score_x"), ptr(score_l, F32, "score_l"),
-                               stream_handle())
-    check(rc, "mdx_mlp_forward")
+    call("mdx_mlp_forward", C.byref(pack.c_struct), atom_types, x, l, time, sigma, B, logits, score_x, score_l)
     return logits, score_x, score_l
 
 
@@ -1025,13 +903,9 @@ def mlp_pc_sample(sched: DeviceSchedule, pack: MlpPack, flags: PcFlags, number_o
     elif workspace is not None and B > 0 and n_iterations > 0:
         work = workspace.get(pack, number_of_corrector_steps, atom_type_transition_in_corrector, n_iterations, B,
                              x.device)
-    rc = lib().mdx_mlp_pc_sample(C.byref(sched.c_struct), C.byref(pack.c_struct), C.byref(flags),
-                                 int(number_of_corrector_steps), int(bool(atom_type_transition_in_corrector)),
-                                 int(start_index), int(n_iterations), rng, B, ptr(atom_types, I64, "atom_types"),
-                                 ptr(x, F32, "x"), ptr(l, F32, "l"), ptr(work, F32, "noise_workspace"),
-                                 0 if work is None else work.numel(), int(options), ptr(status, I32, "status"),
-                                 stream_handle())
-    check(rc, "mdx_mlp_pc_sample")
+    call("mdx_mlp_pc_sample", C.byref(sched.c_struct), C.byref(pack.c_struct), C.byref(flags), int(number_of_corrector_steps),
+         int(bool(atom_type_transition_in_corrector)), int(start_index), int(n_iterations), rng, B, atom_types, x, l, work,
+         0 if work is None else work.numel(), int(options), status)
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -1043,10 +917,7 @@ def egnn_message_input(node_proj, edges, radial, bias, w_radial, silu: bool = Tr
     H = bias.shape[0]
     assert node_proj.shape[1] == 2 * H and radial.numel() == E
     out = torch.empty(E, H, dtype=F32, device=node_proj.device)
-    rc = lib().mdx_egnn_message_input(ptr(node_proj, F32, "node_proj"), ptr(edges, I64, "edges"),
-                                      ptr(radial, F32, "radial"), ptr(bias, F32, "bias"), ptr(w_radial, F32, "w_radial"),
-                                      E, H, int(bool(silu)), ptr(out, F32, "out"), stream_handle())
-    check(rc, "mdx_egnn_message_input")
+    call("mdx_egnn_message_input", node_proj, edges, radial, bias, w_radial, E, H, int(bool(silu)), out)
     return out
 
 
@@ -1056,10 +927,7 @@ def egnn_coord_head(hidden, w_out, coord_diff, offsets, degree, mean: bool) -> t
     if hidden.shape[0] == 0:                                   # no edges at all
         return torch.zeros(n_nodes, d, dtype=F32, device=hidden.device)
     trans = torch.empty(n_nodes, d, dtype=F32, device=hidden.device)
-    rc = lib().mdx_egnn_coord_head(ptr(hidden, F32, "hidden"), ptr(w_out, F32, "w_out"), ptr(coord_diff, F32, "coord_diff"),
-                                   ptr(offsets, I64, "offsets"), ptr(degree, I64, "degree"), n_nodes, H, d,
-                                   int(bool(mean)), ptr(trans, F32, "trans"), stream_handle())
-    check(rc, "mdx_egnn_coord_head")
+    call("mdx_egnn_coord_head", hidden, w_out, coord_diff, offsets, degree, n_nodes, H, d, int(bool(mean)), trans)
     return trans
 
 
@@ -1069,9 +937,7 @@ def segment_rows(data, offsets, degree, mean: bool) -> torch.Tensor:
     if data.shape[0] == 0:
         return torch.zeros(n_nodes, H, dtype=F32, device=data.device)
     out = torch.empty(n_nodes, H, dtype=F32, device=data.device)
-    rc = lib().mdx_segment_rows(ptr(data, F32, "data"), ptr(offsets, I64, "offsets"), ptr(degree, I64, "degree"), n_nodes,
-                                H, int(bool(mean)), ptr(out, F32, "out"), stream_handle())
-    check(rc, "mdx_segment_rows")
+    call("mdx_segment_rows", data, offsets, degree, n_nodes, H, int(bool(mean)), out)
     return out
 
 
@@ -1095,13 +961,11 @@ def _pack_chain_image(weights, w_out, H: int, precision: str, tied_layers: int =
     array = (C.c_void_p * len(keep))(*[w.data_ptr() for w in keep])
     head = None if w_out is None else w_out.detach().reshape(-1).to(F32).contiguous()
     with torch.cuda.device(dev):
-        check(lib().mdx_egnn_chain_pack(array, len(keep), None if head is None else C.c_void_p(head.data_ptr()), H,
-                                        EDGE_CHAIN_PRECISIONS[precision], tied_layers, C.c_void_p(image.data_ptr()),
-                                        C.c_void_p(exponents.data_ptr()), stream_handle()), "mdx_egnn_chain_pack")
+        call("mdx_egnn_chain_pack", array, len(keep), head, H, EDGE_CHAIN_PRECISIONS[precision], tied_layers, image, exponents)
     return image, exponents      # (the temporaries are freed in stream order: the image holds its own copy)
 
 
-F16_ACTIVATION_EXPONENT = 6        # MDX_EGNN_F16_ACTIVATION_EXPONENT
+F16_ACTIVATION_EXPONENT = _hip.EGNN_F16_ACTIVATION_EXPONENT
 
 
 class ActivationScales:
@@ -1119,9 +983,7 @@ class ActivationScales:
 
     def adapt(self):
         with torch.cuda.device(self.exponents.device):
-            check(lib().mdx_egnn_chain_adapt_activation_exponents(C.c_void_p(self.maxima.data_ptr()), self.count,
-                                                                  C.c_void_p(self.exponents.data_ptr()), stream_handle()),
-                  "mdx_egnn_chain_adapt_activation_exponents")
+            call("mdx_egnn_chain_adapt_activation_exponents", self.maxima, self.count, self.exponents)
 
     def reset(self):
         """The state of a new object: default exponents, no maxima.  (The exponents only ever go DOWN otherwise -- after a
@@ -1322,15 +1184,10 @@ def node_mlp_rows(pack: NodeMlpPack, node_in, add_residual: bool, status=None, a
     proj = torch.empty(M, 2 * pack.hidden, dtype=F32, device=node_in.device) if pack.projects else None
     if agg is not None:
         assert W == pack.hidden and agg.shape == node_in.shape
-        rc = lib().mdx_node_mlp_rows_split(C.byref(pack.c_struct), ptr(node_in, F32, "h"), ptr(agg, F32, "agg"),
-                                           int(bool(add_residual)), M, None, ptr(out, F32, "out"), ptr(proj, F32, "proj_out"),
-                                           ptr(status, I32, "status"), stream_handle())
-        check(rc, "mdx_node_mlp_rows_split")
+        call("mdx_node_mlp_rows_split", C.byref(pack.c_struct), node_in, agg, int(bool(add_residual)), M, None, out, proj, status)
         return (out, proj) if pack.projects else out
     assert W == 2 * pack.hidden
-    rc = lib().mdx_node_mlp_rows(C.byref(pack.c_struct), ptr(node_in, F32, "node_in"), int(bool(add_residual)), M, None,
-                                 ptr(out, F32, "out"), ptr(proj, F32, "proj_out"), ptr(status, I32, "status"), stream_handle())
-    check(rc, "mdx_node_mlp_rows")
+    call("mdx_node_mlp_rows", C.byref(pack.c_struct), node_in, int(bool(add_residual)), M, None, out, proj, status)
     return (out, proj) if pack.projects else out
 
 
@@ -1339,9 +1196,7 @@ def mlp_chain_rows(pack: RowChainPack, x, residual=None, status=None) -> torch.T
     M, H = x.shape
     assert H == pack.hidden and (residual is None or residual.shape == x.shape)
     out = torch.empty_like(x)
-    rc = lib().mdx_mlp_chain_rows(C.byref(pack.c_struct), ptr(x, F32, "x"), ptr(residual, F32, "residual"), M, None,
-                                  ptr(out, F32, "out"), ptr(status, I32, "status"), stream_handle())
-    check(rc, "mdx_mlp_chain_rows")
+    call("mdx_mlp_chain_rows", C.byref(pack.c_struct), x, residual, M, None, out, status)
     return out
 
 
@@ -1359,21 +1214,14 @@ def egnn_edge_chain(pack: EdgeChainPack, node_proj, coord, edges, status=None, n
     assert node_proj.shape[1] == 2 * H and coord.shape[0] == node_proj.shape[0]
     if memo is not None:
         assert not piece_sums and sigma is not None and tuple(memo.values.shape) == (E, H)
-        rc = lib().mdx_egnn_edge_chain_keyed(C.byref(pack.c_struct), ptr(node_proj, F32, "node_proj"), ptr(coord, F32, "coord"),
-                                             coord.shape[1], ptr(edges, I64, "edges"), E, ptr(n_edges_dev, I64, "n_edges_dev"),
-                                             ptr(memo.values, F32, "messages"), ptr(memo.scalars, F32, "edge_scalar"),
-                                             ptr(status, I32, "status"), ptr(memo.key, I32, "table_key"),
-                                             ptr(sigma, F32, "sigma"), stream_handle())
-        check(rc, "mdx_egnn_edge_chain_keyed")
+        call("mdx_egnn_edge_chain_keyed", C.byref(pack.c_struct), node_proj, coord, coord.shape[1], edges, E, n_edges_dev,
+             memo.values, memo.scalars, status, memo.key, sigma)
         return memo.values, memo.scalars
     rows = lib().mdx_egnn_piece_rows(E, node_proj.shape[0]) if piece_sums else E
     messages = torch.empty(rows, H, dtype=F32, device=edges.device)
     scalar = torch.empty(E, dtype=F32, device=edges.device)
-    rc = lib().mdx_egnn_edge_chain(C.byref(pack.c_struct), ptr(node_proj, F32, "node_proj"), ptr(coord, F32, "coord"),
-                                   coord.shape[1], ptr(edges, I64, "edges"), E, ptr(n_edges_dev, I64, "n_edges_dev"),
-                                   ptr(messages, F32, "messages"), ptr(scalar, F32, "edge_scalar"),
-                                   ptr(status, I32, "status"), stream_handle())
-    check(rc, "mdx_egnn_edge_chain")
+    call("mdx_egnn_edge_chain", C.byref(pack.c_struct), node_proj, coord, coord.shape[1], edges, E, n_edges_dev, messages, scalar,
+         status)
     return messages, scalar
 
 
@@ -1385,9 +1233,7 @@ def segment_combine(pieces, n_edges: int, offsets, degree, mean: bool, left=None
     assert left is None or tuple(left.shape) == (n_nodes, H)
     assert pieces.shape[0] == lib().mdx_egnn_piece_rows(n_edges, n_nodes), "pieces: not the compact layout of n_edges, n_nodes"
     out = torch.empty(n_nodes, H if left is None else 2 * H, dtype=F32, device=pieces.device)
-    rc = lib().mdx_segment_combine(ptr(pieces, F32, "pieces"), n_edges, ptr(offsets, I64, "offsets"), ptr(degree, I64, "degree"),
-                                   n_nodes, H, int(bool(mean)), ptr(left, F32, "left"), ptr(out, F32, "out"), stream_handle())
-    check(rc, "mdx_segment_combine")
+    call("mdx_segment_combine", pieces, n_edges, offsets, degree, n_nodes, H, int(bool(mean)), left, out)
     return out
 
 
@@ -1404,23 +1250,16 @@ def egnn_node_gather(pieces, n_edges: int, offsets, degree, mean_messages: bool,
     if pieces is None:
         assert left is None
         coord_out = torch.empty_like(coord)
-        rc = lib().mdx_egnn_node_gather(None, n_edges, ptr(offsets, I64, "offsets"), ptr(degree, I64, "degree"), degree.shape[0],
-                                        4, int(bool(mean_messages)), None, None, ptr(edge_scalar, F32, "edge_scalar"),
-                                        ptr(coord, F32, "coord"), coord.shape[1], ptr(edges, I64, "edges"),
-                                        int(bool(mean_coords)), int(flags), ptr(coord_out, F32, "coord_out"), stream_handle())
-        check(rc, "mdx_egnn_node_gather")
+        call("mdx_egnn_node_gather", None, n_edges, offsets, degree, degree.shape[0], 4, int(bool(mean_messages)), None, None,
+             edge_scalar, coord, coord.shape[1], edges, int(bool(mean_coords)), int(flags), coord_out)
         return None, coord_out
     n_nodes, H = degree.shape[0], pieces.shape[1]
     assert left is None or tuple(left.shape) == (n_nodes, H)
     assert pieces.shape[0] == lib().mdx_egnn_piece_rows(n_edges, n_nodes), "pieces: not the compact layout of n_edges, n_nodes"
     out = torch.empty(n_nodes, H if left is None else 2 * H, dtype=F32, device=pieces.device)
     coord_out = torch.empty_like(coord)
-    rc = lib().mdx_egnn_node_gather(ptr(pieces, F32, "pieces"), n_edges, ptr(offsets, I64, "offsets"), ptr(degree, I64, "degree"),
-                                    n_nodes, H, int(bool(mean_messages)), ptr(left, F32, "left"), ptr(out, F32, "out"),
-                                    ptr(edge_scalar, F32, "edge_scalar"), ptr(coord, F32, "coord"), coord.shape[1],
-                                    ptr(edges, I64, "edges"), int(bool(mean_coords)), int(flags),
-                                    ptr(coord_out, F32, "coord_out"), stream_handle())
-    check(rc, "mdx_egnn_node_gather")
+    call("mdx_egnn_node_gather", pieces, n_edges, offsets, degree, n_nodes, H, int(bool(mean_messages)), left, out, edge_scalar,
+         coord, coord.shape[1], edges, int(bool(mean_coords)), int(flags), coord_out)
     return out, coord_out
 
 
@@ -1432,7 +1271,7 @@ TABLE_INV_SPACING = 256.0        # h = 2^-8 between the even grid points: rho_k 
 TABLE_TOLERANCE = 2.0 ** -16
 
 
-TABLE_NO_KEY = 0x7fc00000        # MDX_EGNN_TABLE_NO_KEY: a NaN's bits in the key record = no table in memory
+TABLE_NO_KEY = _hip.EGNN_TABLE_NO_KEY        # a NaN's bits in the key record = no table in memory
 
 
 class EgnnTableMemo:
@@ -1517,11 +1356,8 @@ def egnn_table_check(table, table_scalar, n_classes: int, n_even: int, sigma, wo
     check always, and the key record written last."""
     H = table.shape[1]
     assert table.shape[0] == n_classes * n_classes * (2 * n_even - 1) and workspace.numel() >= n_classes ** 2 * (H + 2)
-    rc = lib().mdx_egnn_table_check_keyed(ptr(table, F32, "table"), ptr(table_scalar, F32, "table_scalar"), H, n_classes, n_even,
-                                          ptr(sigma, F32, "sigma"), sigma.numel(), TABLE_TOLERANCE,
-                                          ptr(workspace, I32, "workspace"), ptr(worst, F32, "worst"), ptr(status, I32, "status"),
-                                          ptr(key, I32, "table_key"), stream_handle())
-    check(rc, "mdx_egnn_table_check_keyed")
+    call("mdx_egnn_table_check_keyed", table, table_scalar, H, n_classes, n_even, sigma, sigma.numel(), TABLE_TOLERANCE, workspace,
+         worst, status, key)
 
 
 def egnn_table_gather(table, table_scalar, n_classes: int, n_even: int, atom_types, offsets, degree, mean_messages: bool, left,
@@ -1532,13 +1368,9 @@ def egnn_table_gather(table, table_scalar, n_classes: int, n_even: int, atom_typ
     assert atom_types.shape[0] == n_nodes and table.shape[0] == n_classes * n_classes * (2 * n_even - 1)
     out = torch.empty(n_nodes, H if left is None else 2 * H, dtype=F32, device=table.device)
     coord_out = torch.empty_like(coord)
-    rc = lib().mdx_egnn_table_gather(ptr(table, F32, "table"), ptr(table_scalar, F32, "table_scalar"), H, n_classes, n_even,
-                                     TABLE_INV_SPACING, ptr(atom_types, I64, "atom_types"), ptr(offsets, I64, "offsets"),
-                                     ptr(degree, I64, "degree"), n_nodes, int(bool(mean_messages)), ptr(left, F32, "left"),
-                                     ptr(out, F32, "out"), ptr(coord, F32, "coord"), coord.shape[1], ptr(edges, I64, "edges"),
-                                     int(bool(mean_coords)), int(flags), ptr(coord_out, F32, "coord_out"),
-                                     ptr(status, I32, "status"), stream_handle())
-    check(rc, "mdx_egnn_table_gather")
+    call("mdx_egnn_table_gather", table, table_scalar, H, n_classes, n_even, TABLE_INV_SPACING, atom_types, offsets, degree,
+         n_nodes, int(bool(mean_messages)), left, out, coord, coord.shape[1], edges, int(bool(mean_coords)), int(flags), coord_out,
+         status)
     return out, coord_out
 
 
@@ -1562,13 +1394,8 @@ def egnn_node_inputs(x, k_vectors, sigma, atom_types, emb_weight, emb_bias, seco
         z = torch.empty(n_nodes, 2 * n_k, dtype=F32, device=x.device)
         h = torch.empty(n_nodes, H, dtype=F32, device=x.device)
         h2 = torch.empty(n_nodes, H2, dtype=F32, device=x.device) if second is not None else None
-    rc = lib().mdx_egnn_node_inputs_keyed(ptr(x, F32, "x"), ptr(k_vectors, F32, "k_vectors"), n_k, ptr(sigma, F32, "sigma"), N,
-                                          ptr(atom_types, I64, "atom_types"), ptr(emb_weight, F32, "emb_weight"),
-                                          ptr(emb_bias, F32, "emb_bias"), F, H, n_nodes, ptr(z, F32, "z"), ptr(h, F32, "h"),
-                                          ptr(w2, F32, "second_weight"), ptr(b2, F32, "second_bias"), H2,
-                                          ptr(h2, F32, "second_out"), ptr(memo.key if memo is not None else None, I32, "table_key"),
-                                          stream_handle())
-    check(rc, "mdx_egnn_node_inputs_keyed")
+    call("mdx_egnn_node_inputs_keyed", x, k_vectors, n_k, sigma, N, atom_types, emb_weight, emb_bias, F, H, n_nodes, z, h, w2, b2,
+         H2, h2, memo.key if memo is not None else None)
     return (z, h) if second is None else (z, h, h2)
 
 
@@ -1577,9 +1404,7 @@ def egnn_scores(z, x_hat, k_vectors):
     n_nodes, n_k = z.shape[0], k_vectors.shape[0]
     assert z.shape == x_hat.shape == (n_nodes, 2 * n_k)
     out = torch.empty(n_nodes, 3, dtype=F32, device=z.device)
-    rc = lib().mdx_egnn_scores(ptr(z, F32, "z"), ptr(x_hat, F32, "x_hat"), ptr(k_vectors, F32, "k_vectors"), n_k, n_nodes,
-                               ptr(out, F32, "scores"), stream_handle())
-    check(rc, "mdx_egnn_scores")
+    call("mdx_egnn_scores", z, x_hat, k_vectors, n_k, n_nodes, out)
     return out
 
 
@@ -1591,22 +1416,16 @@ def egnn_outputs(z, x_hat, k_vectors, h, class_weight, class_bias, mask_class: i
     scores = torch.empty(n_nodes, 3, dtype=F32, device=z.device)
     logits = torch.empty(n_nodes, C, dtype=F32, device=z.device)
     zeros = torch.empty(int(n_zero), dtype=F32, device=z.device)
-    rc = lib().mdx_egnn_outputs(ptr(z, F32, "z"), ptr(x_hat, F32, "x_hat"), ptr(k_vectors, F32, "k_vectors"), n_k,
-                                ptr(h, F32, "h"), ptr(class_weight, F32, "class_weight"), ptr(class_bias, F32, "class_bias"),
-                                H, C, int(mask_class), n_nodes, ptr(scores, F32, "scores"), ptr(logits, F32, "logits"),
-                                ptr(zeros, F32, "zeros") if n_zero else None, int(n_zero), stream_handle())
-    check(rc, "mdx_egnn_outputs")
+    call("mdx_egnn_outputs", z, x_hat, k_vectors, n_k, h, class_weight, class_bias, H, C, int(mask_class), n_nodes, scores, logits,
+         zeros if n_zero else None, int(n_zero))
     return scores, logits, zeros
 
 
 def egnn_coord_aggregate(edge_scalar, coord, edges, offsets, degree, mean: bool, flags: int = 0) -> torch.Tensor:
     """coord + segment sum/mean of (coord_i - coord_dst) * edge_scalar over each node's sorted edges (flags: coord_flags())."""
     out = torch.empty_like(coord)
-    rc = lib().mdx_egnn_coord_aggregate(ptr(edge_scalar, F32, "edge_scalar"), ptr(coord, F32, "coord"), coord.shape[1],
-                                        ptr(edges, I64, "edges"), ptr(offsets, I64, "offsets"), ptr(degree, I64, "degree"),
-                                        coord.shape[0], int(bool(mean)), int(flags), ptr(out, F32, "coord_out"),
-                                        stream_handle())
-    check(rc, "mdx_egnn_coord_aggregate")
+    call("mdx_egnn_coord_aggregate", edge_scalar, coord, coord.shape[1], edges, offsets, degree, coord.shape[0], int(bool(mean)),
+         int(flags), out)
     return out
 
 
@@ -1618,13 +1437,11 @@ RNG_UNIFORM, RNG_NORMAL, RNG_GUMBEL = 0, 1, 2
 
 def rng_fill(kind: int, seed: int, call: int, draw: int, tag: int, n_items: int, width: int, device) -> torch.Tensor:
     out = torch.empty(n_items, width, dtype=F32, device=device)
-    rc = lib().mdx_rng_fill(kind, int(seed) & 0xFFFFFFFFFFFFFFFF, int(call), int(draw), int(tag), n_items, width,
-                            ptr(out, F32, "out"), stream_handle())
-    check(rc, "mdx_rng_fill")
+    _hip.call("mdx_rng_fill", kind, int(seed) & 0xFFFFFFFFFFFFFFFF, int(call), int(draw), int(tag), n_items, width, out)
     return out
 
 
 def math_probe(fn: int, x: torch.Tensor) -> torch.Tensor:
     y = torch.empty_like(x)
-    check(lib().mdx_math_probe(fn, ptr(x, F32, "x"), x.numel(), ptr(y, F32, "y"), stream_handle()), "mdx_math_probe")
+    call("mdx_math_probe", fn, x, x.numel(), y)
     return y
