@@ -5,7 +5,9 @@ and contiguity of each against the header's parameter, appends torch's current H
 and returns torch tensors that PyTorch owns.  Nothing here computes on the CPU.
 """
 import ctypes as C
+from collections import namedtuple
 from dataclasses import dataclass
+from functools import lru_cache
 from typing import Optional
 
 import torch
@@ -680,6 +682,139 @@ def optimal_translation(x, y, with_details: bool = False, status: Optional[torch
     number_of_candidates = torch.empty(B, D, dtype=I32, device=dev) if with_details else None
     call("mdx_optimal_translation", x, stride, y, B, N, D, tau, squared_distance, number_of_candidates, status)
     return (tau, squared_distance, number_of_candidates) if with_details else tau
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# denoising loss (csrc/mdx_loss.hip)
+# ----------------------------------------------------------------------------------------------------------------
+LOSS_ALGORITHMS = {"mse": _hip.LOSS_MSE, "weighted_mse": _hip.LOSS_WEIGHTED_MSE}
+LOSS_MAX_ATOMS, LOSS_MAX_LATTICE_PARAMETERS = _hip.LOSS_MAX_ATOMS, _hip.LOSS_MAX_LATTICE_PARAMETERS
+LOSS_LOGITS_MESSAGE = "Logits are pathological: the probabilities do not sum to one."
+
+DenoisingLoss = namedtuple("DenoisingLoss", ["target_x", "target_l", "loss_x", "loss_a", "loss_l", "per_structure", "q_atm1",
+                                             "p_atm1", "vb_term", "ce_term"])
+
+
+def binary32(value: float) -> float:
+    """The binary32 neighbour of a Python float, as a Python float: what a 0-dim float32 buffer of the reference holds."""
+    return float(torch.tensor(value, dtype=F32))
+
+
+@lru_cache(maxsize=None)
+def root_of_atom_count(number_of_atoms: int, degree: int) -> float:
+    """n^(1 / degree) as the reference's scale_sigma_by_number_of_atoms makes it (utils/noise_utils.py:29): torch.pow of a
+    binary32 HOST tensor, so that a sigma_n made from it has the reference's bits whatever the device's pow rounds to."""
+    return float(torch.pow(torch.full((16,), float(number_of_atoms)), 1 / degree)[0])
+
+
+def raise_loss_status(status: torch.Tensor):
+    """One host read of a status word mdx_denoising_loss reported into: its bits are cleared, then raised -- the reference's
+    value assertion on the logits (utils/d3pm_utils.py:144-145), the wrapped score's two, and an index outside its table."""
+    own = _hip.STATUS_LOSS_LOGITS | _hip.STATUS_LOSS_INDEX | _hip.STATUS_ANALYTICAL_SIGMA | _hip.STATUS_ANALYTICAL_COORDINATES
+    word = int(status.item())
+    if word & own:
+        status.bitwise_and_(~own)
+    if word & _hip.STATUS_LOSS_LOGITS:
+        raise AssertionError(LOSS_LOGITS_MESSAGE)
+    if word & _hip.STATUS_LOSS_INDEX:
+        raise IndexError("a time index outside the transition tables or an atom type outside [0, num_classes)")
+    raise_analytical_bits(word)
+
+
+def denoising_loss(*, x0=None, xt=None, target_x=None, predicted_x=None, sigma=None, a0=None, at=None, logits=None,
+                   time_indices=None, q_matrices=None, q_bar_matrices=None, q_bar_tm1_matrices=None,
+                   tables_per_structure: bool = False, l0=None, lt=None, predicted_l=None, sigma_n=None, sigma_n_divisor: float = 0.0,
+                   kmax: int = 4,
+                   x_algorithm: str = "mse", x_sigma0: float = 0.0, x_exponent: float = 0.0, l_algorithm: str = "mse",
+                   l_sigma0: float = 0.0, l_exponent: float = 0.0, ce_weight: float = 0.001, eps: float = 1e-8,
+                   lambda_weights=(1.0, 1.0, 1.0), with_terms: bool = False,
+                   status: Optional[torch.Tensor] = None) -> DenoisingLoss:
+    """The denoising loss of a noised batch in one launch (mdx_denoising_loss), no host read.  The three parts are independent,
+    each present when its prediction (for A: a0) is given:
+      X  predicted_x f32 [B, N, D]; sigma f32 with B elements, or [B, N, D]; the target from x0, xt f32 [B, N, D] (kmax), or
+         `target_x` f32 [B, N, D] as given
+      A  a0, at int64 [B, N], logits f32 [B, N, C], time_indices int64 [B]; the three transition tables f32 [T, C, C], read at
+         the structure's time index, or with `tables_per_structure` [B, C, C], one row per structure.  Without tables only
+         ce_term is made, without logits only q_atm1
+      L  l0, lt, predicted_l f32 [B, P]; sigma_n f32 with B elements, or `sigma_n_divisor`: sigma_n = sigma / divisor in
+         binary32 inside the kernel; the weights of weighted_mse take `sigma`
+    x_sigma0, x_exponent, l_sigma0, l_exponent go to the kernel as given: the reference holds them in binary32 (`binary32`).
+    lambda_weights is (A, X, L).  Returns a DenoisingLoss of f32 tensors, None where its part is absent: the two targets, the
+    three unreduced losses, per_structure [B, 4] = (mean A, mean X, mean L, weighted aggregate), and with `with_terms` the
+    atom-type intermediates q_atm1, p_atm1, vb_term, ce_term [B, N, C]."""
+    _device_only("the denoising loss", x0=x0, xt=xt, target_x=target_x, predicted_x=predicted_x, sigma=sigma, a0=a0, at=at,
+                 logits=logits, time_indices=time_indices, q_matrices=q_matrices, q_bar_matrices=q_bar_matrices,
+                 q_bar_tm1_matrices=q_bar_tm1_matrices, l0=l0, lt=lt, predicted_l=predicted_l, sigma_n=sigma_n, status=status)
+    with_x, with_a, with_l = predicted_x is not None, a0 is not None, predicted_l is not None
+    leading = predicted_x if with_x else a0 if with_a else predicted_l
+    if leading is None:
+        raise ValueError("one of predicted_x, a0 and predicted_l must be given")
+    B, dev = leading.shape[0], leading.device
+    N, D, Cn, P, T, per_element = 1, 1, 0, 0, 0, 0
+
+    def expect(name, t, shape):
+        if t is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+
+    def per_structure_values(name, t):
+        if t is not None and t.numel() != B:
+            raise ValueError(f"{name} has shape {tuple(t.shape)}: expected one value per structure, [{B}]")
+
+    def empty(present, *shape):
+        return torch.empty(*shape, dtype=F32, device=dev) if present else None
+
+    if with_x:
+        if predicted_x.dim() != 3:
+            raise ValueError(f"predicted_x has shape {tuple(predicted_x.shape)}, expected [B, N, D]")
+        _, N, D = predicted_x.shape
+        for name, t in (("x0", x0), ("xt", xt), ("target_x", target_x)):
+            expect(name, t, (B, N, D))
+        if target_x is None and (x0 is None or xt is None or sigma is None):
+            raise ValueError("the coordinates' part needs x0, xt and sigma, or target_x")
+    if sigma is not None:
+        per_element = int(with_x and sigma.numel() != B and tuple(sigma.shape) == (B, N, D))
+        if not per_element:
+            per_structure_values("sigma", sigma)
+    if with_a:
+        if a0.dim() != 2 or (with_x and tuple(a0.shape) != (B, N)):
+            raise ValueError(f"a0 has shape {tuple(a0.shape)}, expected {(B, N) if with_x else '[B, N]'}")
+        N = a0.shape[1]
+        tables = (q_matrices, q_bar_matrices, q_bar_tm1_matrices)
+        if logits is None and tables[0] is None:
+            raise ValueError("the atom types' part needs logits or the transition tables")
+        Cn = logits.shape[-1] if logits is not None else tables[0].shape[-1]
+        expect("at", at, (B, N))
+        expect("logits", logits, (B, N, Cn))
+        expect("time_indices", time_indices, (B,))
+        if any(t is not None for t in tables):
+            if any(t is None for t in tables) or at is None or time_indices is None:
+                raise ValueError("the transition tables come as three, with at and time_indices")
+            T = 0 if tables_per_structure else tables[0].shape[0]
+            for name, t in zip(("q_matrices", "q_bar_matrices", "q_bar_tm1_matrices"), tables):
+                expect(name, t, (B if tables_per_structure else T, Cn, Cn))
+    if with_l:
+        if predicted_l.dim() != 2:
+            raise ValueError(f"predicted_l has shape {tuple(predicted_l.shape)}, expected [B, P]")
+        P = predicted_l.shape[1]
+        for name, t in (("l0", l0), ("lt", lt)):
+            expect(name, t, (B, P))
+        if l0 is None or lt is None or (sigma_n is None and not (sigma is not None and sigma_n_divisor > 0.0)):
+            raise ValueError("the lattice parameters' part needs l0, lt and sigma_n (or sigma and sigma_n_divisor)")
+        per_structure_values("sigma_n", sigma_n)
+    with_tables = with_a and q_matrices is not None
+    with_logits = with_a and logits is not None
+    out = DenoisingLoss(
+        target_x=empty(with_x and target_x is None, B, N, D), target_l=empty(with_l, B, P), loss_x=empty(with_x, B, N, D),
+        loss_a=empty(with_tables and with_logits, B, N, Cn), loss_l=empty(with_l, B, P), per_structure=empty(True, B, 4),
+        q_atm1=empty(with_terms and with_tables, B, N, Cn), p_atm1=empty(with_terms and with_tables and with_logits, B, N, Cn),
+        vb_term=empty(with_terms and with_tables and with_logits, B, N, Cn), ce_term=empty(with_terms and with_logits, B, N, Cn))
+    lambda_a, lambda_x, lambda_l = (float(w) for w in lambda_weights)
+    call("mdx_denoising_loss", x0, xt, target_x, predicted_x, sigma, per_element, a0, at, logits, time_indices, q_matrices,
+         q_bar_matrices, q_bar_tm1_matrices, int(T), l0, lt, predicted_l, sigma_n, float(sigma_n_divisor), B, int(N), int(D), int(Cn), int(P), int(kmax),
+         LOSS_ALGORITHMS[x_algorithm], float(x_sigma0), float(x_exponent), LOSS_ALGORITHMS[l_algorithm], float(l_sigma0),
+         float(l_exponent), float(ce_weight), float(eps), lambda_a, lambda_x, lambda_l, out.target_x, out.target_l, out.loss_x,
+         out.loss_a, out.loss_l, out.per_structure, out.q_atm1, out.p_atm1, out.vb_term, out.ce_term, status)
+    return out
 
 
 # ----------------------------------------------------------------------------------------------------------------

@@ -1,0 +1,104 @@
+"""The loss calculators' factory (src/.../loss/__init__.py:7-41) and `denoising_loss`, the loss of a score network on a noised
+batch: what the reference's AXLDiffusionLightningModel._generic_step (models/axl_diffusion_lightning_model.py:186-381) returns
+for a test or validation batch, made by ONE launch of the fused loss kernel after the network's forward."""
+from typing import Any, Dict, Optional
+
+import torch
+
+from .. import kernels
+from ..namespace import (ATOM_TYPES, AXL, AXL_COMPOSITION, CARTESIAN_FORCES, LATTICE_PARAMETERS, NOISE, NOISY_ATOM_TYPES,
+                         NOISY_AXL_COMPOSITION, NOISY_LATTICE_PARAMETERS, NOISY_RELATIVE_COORDINATES, Q_BAR_MATRICES,
+                         Q_BAR_TM1_MATRICES, Q_MATRICES, RELATIVE_COORDINATES, TIME, TIME_INDICES)
+from .atom_type_loss_calculator import D3PMLossCalculator
+from .coordinates_loss_calculator import MSELossCalculator, WeightedMSELossCalculator
+from .loss_parameters import create_loss_parameters
+
+LOSS_BY_ALGO = dict(mse=MSELossCalculator, weighted_mse=WeightedMSELossCalculator)
+
+
+def create_loss_calculator(loss_parameters: AXL) -> AXL:
+    """The calculators of the atom types, coordinates and lattice parameters in an AXL  (:10-41)."""
+    coordinates_algorithm = loss_parameters.X.algorithm
+    assert coordinates_algorithm in LOSS_BY_ALGO.keys(), \
+        f"Algorithm {coordinates_algorithm} is not implemented. Possible choices are {LOSS_BY_ALGO.keys()}"
+    lattice_algorithm = loss_parameters.L.algorithm
+    assert lattice_algorithm in LOSS_BY_ALGO.keys(), \
+        f"Algorithm {lattice_algorithm} is not implemented. Possible choices are {LOSS_BY_ALGO.keys()}"
+    return AXL(A=D3PMLossCalculator(loss_parameters.A), X=LOSS_BY_ALGO[coordinates_algorithm](loss_parameters.X),
+               L=LOSS_BY_ALGO[lattice_algorithm](loss_parameters.L))
+
+
+def _per_structure_rows(matrices: torch.Tensor) -> torch.Tensor:
+    """[batch, classes, classes] of a noised batch's [batch, atoms, classes, classes] matrices: the rows NoisingTransform's
+    expand() views share (no copy), else the first atom's -- the matrices are the same for all atoms of a structure
+    (data/diffusion/noising_transform.py:160-162)."""
+    return matrices if matrices.dim() == 3 else matrices[:, 0].contiguous()
+
+
+def _weighted_scalars(prefix: str, parameters) -> dict:
+    if parameters.algorithm not in LOSS_BY_ALGO:
+        raise AssertionError(f"Algorithm {parameters.algorithm} is not implemented. Possible choices are {LOSS_BY_ALGO.keys()}")
+    scalars = {prefix + "algorithm": parameters.algorithm}
+    if parameters.algorithm == "weighted_mse":       # 0-dim float32 buffers in the reference: their binary32 values
+        scalars[prefix + "sigma0"] = kernels.binary32(parameters.sigma0)
+        scalars[prefix + "exponent"] = kernels.binary32(parameters.exponent)
+    return scalars
+
+
+_STATUS = {}
+
+
+def _status_word(device: torch.device) -> torch.Tensor:
+    if device not in _STATUS:
+        _STATUS[device] = torch.zeros(1, dtype=torch.int32, device=device)
+    return _STATUS[device]
+
+
+def denoising_loss(axl_network, noised_batch: Dict[str, Any], loss_parameters: Optional[AXL] = None, kmax_target_score: int = 4,
+                   conditional: Optional[bool] = None) -> dict:
+    """The denoising loss of `axl_network` on a batch NoisingTransform noised (device tensors only).
+
+    Returns _generic_step's dictionary: `unreduced_loss` (AXL of [B, N, C], [B, N, D], [B, P]), `loss` (0-dim), `sigmas`
+    [B, N, D], `model_predictions` (AXL), `target_coordinates_normalized_conditional_scores`,
+    `target_lattice_normalized_conditional_scores`, AXL_COMPOSITION, NOISY_AXL_COMPOSITION and TIME; and beside them
+    `per_structure_loss` [B], the weighted aggregate of every structure (`loss` is its mean), and `status`, the device word
+    the kernel reports the reference's value assertions into: nothing here reads it; kernels.raise_loss_status(status) does.
+    The weights are the three lambda_weight of `loss_parameters` (default: create_loss_parameters({})).  `conditional` goes to
+    the network's forward as it is."""
+    parameters = create_loss_parameters({}) if loss_parameters is None else loss_parameters
+    a0, x0, l0 = noised_batch[ATOM_TYPES], noised_batch[RELATIVE_COORDINATES], noised_batch[LATTICE_PARAMETERS]
+    at, xt, lt = noised_batch[NOISY_ATOM_TYPES], noised_batch[NOISY_RELATIVE_COORDINATES], noised_batch[NOISY_LATTICE_PARAMETERS]
+    noise, time_indices = noised_batch[NOISE], noised_batch[TIME_INDICES]
+    tables = [noised_batch[key] for key in (Q_MATRICES, Q_BAR_MATRICES, Q_BAR_TM1_MATRICES)]
+    kernels._device_only("the denoising loss", atom_types=a0, relative_coordinates=x0, lattice_parameters=l0, noisy_atom_types=at,
+                         noisy_relative_coordinates=xt, noisy_lattice_parameters=lt, noise_parameter=noise,
+                         time_indices=time_indices, q_matrices=tables[0], q_bar_matrices=tables[1], q_bar_tm1_matrices=tables[2])
+    composition, noisy_composition = AXL(A=a0, X=x0, L=l0), AXL(A=at, X=xt, L=lt)
+    B, N, D = x0.shape
+    forces = noised_batch[CARTESIAN_FORCES] if CARTESIAN_FORCES in noised_batch else torch.zeros_like(x0)
+    augmented_batch = {NOISY_AXL_COMPOSITION: noisy_composition, TIME: noised_batch[TIME], NOISE: noise, CARTESIAN_FORCES: forces}
+    predictions = axl_network(augmented_batch, conditional=conditional)
+    predictions = AXL(A=predictions.A.detach(), X=predictions.X.detach(), L=predictions.L.detach())
+    status = _status_word(x0.device)
+    # sigma_n = sigma / N^(1/P) inside the kernel: the reference scales by the number of lattice parameters here
+    # (models/axl_diffusion_lightning_model.py:275-277), not by the spatial dimension
+    out = kernels.denoising_loss(
+        x0=x0.contiguous(), xt=xt.contiguous(), predicted_x=predictions.X.contiguous(), sigma=noise.reshape(B).contiguous(),
+        a0=a0.contiguous(), at=at.contiguous(), logits=predictions.A.contiguous(), time_indices=time_indices.contiguous(),
+        q_matrices=_per_structure_rows(tables[0]), q_bar_matrices=_per_structure_rows(tables[1]),
+        q_bar_tm1_matrices=_per_structure_rows(tables[2]), tables_per_structure=True,
+        l0=l0.contiguous(), lt=lt.contiguous(), predicted_l=predictions.L.contiguous(),
+        sigma_n_divisor=kernels.root_of_atom_count(N, l0.shape[-1]), kmax=kmax_target_score,
+        **_weighted_scalars("x_", parameters.X), **_weighted_scalars("l_", parameters.L), ce_weight=parameters.A.ce_weight,
+        eps=parameters.A.eps, lambda_weights=(parameters.A.lambda_weight, parameters.X.lambda_weight, parameters.L.lambda_weight),
+        status=status)
+    per_structure_loss = out.per_structure[:, 3]
+    output = dict(unreduced_loss=AXL(A=out.loss_a, X=out.loss_x, L=out.loss_l),
+                  loss=per_structure_loss.mean(dtype=torch.float64).to(torch.float32),
+                  sigmas=noise.reshape(B, 1, 1).expand(B, N, D), model_predictions=predictions,
+                  target_coordinates_normalized_conditional_scores=out.target_x,
+                  target_lattice_normalized_conditional_scores=out.target_l, per_structure_loss=per_structure_loss, status=status)
+    output[AXL_COMPOSITION] = composition
+    output[NOISY_AXL_COMPOSITION] = noisy_composition
+    output[TIME] = augmented_batch[TIME]
+    return output

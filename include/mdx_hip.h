@@ -71,6 +71,12 @@ extern "C" {
 #define MDX_STATUS_TRANSLATION_NO_CANDIDATE 32768u /* mdx_optimal_translation: no plateau holds its own solution (the minimum sits
                                             on the boundary tau = +-1/2); that entry's tau and squared distance are +inf   */
 
+#define MDX_STATUS_LOSS_LOGITS 65536u     /* mdx_denoising_loss: the softmax of an atom's logits does not sum to one (a NaN or
+                                            +inf logit, or every logit -inf: utils/d3pm_utils.py:144-145 assert); that atom's
+                                            atom-type results are NaN                                                       */
+#define MDX_STATUS_LOSS_INDEX 131072u    /* the same function: a time index outside [0, T) or an atom type outside [0, C); the
+                                            structure's (atom's) atom-type results are NaN and no table entry is read       */
+
 #define MDX_MAX_CLASSES 8      /* C supported by the fused atom-type kernels */
 #define MDX_PREDICTOR 0
 #define MDX_CORRECTOR 1
@@ -576,6 +582,51 @@ MDX_API int mdx_equivariant_analytical_score(const float* relative_coordinates, 
                                              int number_of_operations, double sigma_d_square, int kmax, int64_t batch,
                                              int number_of_atoms, int spatial_dimension, float* sigma_normalized_scores,
                                              uint32_t* status, mdx_stream_t stream);
+
+/* The denoising loss of a score network on a noised batch in one launch (csrc/mdx_loss.hip): what
+ * AXLDiffusionLightningModel._generic_step (models/axl_diffusion_lightning_model.py:243-346) computes after the network's
+ * forward -- the two targets, the three unreduced losses of loss/coordinates_loss_calculator.py and
+ * loss/atom_type_loss_calculator.py (on utils/d3pm_utils.py), their per-structure means and the weighted aggregate.  One
+ * workgroup per structure; N <= MDX_LOSS_MAX_ATOMS, D <= 3, C <= MDX_MAX_CLASSES, P <= MDX_LOSS_MAX_LATTICE_PARAMETERS and
+ * kmax <= 64, else MDX_ERR_UNSUPPORTED (before anything is launched).  Binary64 from the binary32 inputs promoted once, every
+ * output value rounded once; no atomics in the arithmetic and every sum in a fixed order: the same bits on every launch and
+ * hipGraph replay.  No host read.  The three parts are independent; a part whose prediction pointer is NULL is left out (its
+ * outputs must be NULL, its mean is 0 and it adds nothing to the aggregate):
+ *   X  predicted_x f32 [batch, N, D]; sigma f32 [batch] (sigma_per_element 0) or [batch, N, D] (1).  The target is
+ *      target_x_in f32 [batch, N, D] when given, else sigma x score of the wrapped Gaussian at u = wrap(xt - x0) with the
+ *      reference's formulas and truncation kmax (mdx_wrapped_gaussian_sigma_normalized_score), from x0, xt f32 [batch, N, D];
+ *      loss = (predicted - target)^2, times exp(x_exponent (sigma - x_sigma0)) + 1 when x_algorithm is MDX_LOSS_WEIGHTED_MSE.
+ *      The reference keeps sigma0 and exponent as BINARY32 buffers: pass the binary32-rounded values.  A sigma that is not
+ *      finite and positive or a coordinate that is not finite gives NaN and MDX_STATUS_ANALYTICAL_SIGMA / _COORDINATES.
+ *   A  a0 int64 [batch, N] (a_0), at int64 [batch, N] (a_t), logits f32 [batch, N, C] (class C - 1 is MASK), time_indices int64
+ *      [batch]; the three transition tables f32 [T, C, C] with T = total_time_steps, read at the structure's time index, or with
+ *      total_time_steps 0 f32 [batch, C, C], read at the structure's own number.  p = the softmax of the logits clipped at eps
+ *      and renormalised; ce = -log_softmax with the MASK column forced to 0, kept at a_0; q(a_{t-1} | a_t, a_0) and
+ *      p(a_{t-1} | a_t) by (gamma Qbar_{t-1})_i (Q_t)_{i, a_t} / (gamma Qbar_t)_{a_t} with gamma = one-hot a_0 and gamma = p;
+ *      vb = xlogy(q, q) - q log(max(p(a_{t-1} | a_t), eps)) (a target of 0 gives 0), and at time index 0 -log(..) kept at a_0;
+ *      loss = vb + ce_weight ce.  Without tables only ce_term is made, without logits only q_atm1; at is needed with tables.
+ *   L  l0, lt, predicted_l f32 [batch, P]; sigma_n f32 [batch], or NULL: then sigma_n = sigma / sigma_n_divisor, one binary32
+ *      division (utils/noise_utils.py:29 on binary32 tensors; the divisor is n^(1/d)).  target = -(lt - l0) / sigma_n; the loss as
+ *      for X with l_algorithm, l_sigma0, l_exponent and the structure's sigma (NOT sigma_n:
+ *      models/axl_diffusion_lightning_model.py:319-323).
+ * Outputs, f32, each nullable: target_x, loss_x [batch, N, D]; loss_a, q_atm1, p_atm1, vb_term, ce_term [batch, N, C]; target_l,
+ * loss_l [batch, P]; per_structure [batch, 4] = the means of loss_a, loss_x, loss_l over the structure (taken in binary64) and
+ * lambda_x mean_x + lambda_l mean_l + lambda_a mean_a.  status (nullable) receives the bits named above. */
+#define MDX_LOSS_MSE 0
+#define MDX_LOSS_WEIGHTED_MSE 1
+#define MDX_LOSS_MAX_ATOMS 1024
+#define MDX_LOSS_MAX_LATTICE_PARAMETERS 6
+MDX_API int mdx_denoising_loss(const float* x0, const float* xt, const float* target_x_in, const float* predicted_x,
+                               const float* sigma, int sigma_per_element, const int64_t* a0, const int64_t* at,
+                               const float* logits, const int64_t* time_indices, const float* q_matrices,
+                               const float* q_bar_matrices, const float* q_bar_tm1_matrices, int total_time_steps,
+                               const float* l0, const float* lt, const float* predicted_l, const float* sigma_n, float sigma_n_divisor,
+                               int64_t batch, int number_of_atoms, int spatial_dimension, int num_classes, int number_of_lattice_parameters,
+                               int kmax, int x_algorithm, double x_sigma0, double x_exponent, int l_algorithm, double l_sigma0,
+                               double l_exponent, double ce_weight, double eps, double lambda_a, double lambda_x,
+                               double lambda_l, float* target_x, float* target_l, float* loss_x, float* loss_a, float* loss_l,
+                               float* per_structure, float* q_atm1, float* p_atm1, float* vb_term, float* ce_term,
+                               uint32_t* status, mdx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Fused score network: the reference's MLPScoreNetwork (models/score_networks/mlp_score_network.py:54-370,
