@@ -20,6 +20,7 @@
 #include "../../include/mdx_hip.h"
 #include "mdx_launch.hpp"
 #include "mdx_math.hpp"
+#include "mdx_reduce.hpp"
 #include "mdx_wrapped_score.hpp"
 
 using namespace mdx;
@@ -34,19 +35,7 @@ constexpr int kMaxTranslation = 64;           // kmax: the sums run over 2 kmax 
 constexpr int kTerms = kMaxPermutedAtoms * kMaxDimension;
 constexpr int kBadSigma = 1, kBadCoordinate = 2;
 
-__device__ __forceinline__ bool finite_(double v) { return __builtin_fabs(v) < 1.0e300; }
-__device__ __forceinline__ bool sigma_valid(double s) { return s > 0.0 && finite_(s); }
 __device__ __forceinline__ bool coordinate_valid(double x) { return x >= 0.0 && x < 1.0; }
-
-__device__ __forceinline__ double wave_max(double v)
-{
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        const double w = __shfl_xor(v, o, kWave);
-        v = w > v ? w : v;
-    }
-    return v;
-}
 
 __global__ __launch_bounds__(kBlock) void wrapped_gaussian_score_kernel(const float* __restrict__ u, const float* __restrict__ sigma,
                                                                         int64_t n, int kmax, int coordinates_bounded,
@@ -88,20 +77,6 @@ __global__ __launch_bounds__(kBlock) void log_wrapped_gaussians_kernel(const flo
         }
         out[r] = (float)sum;
     }
-}
-
-// the sum of one value per thread over the workgroup, in a fixed order: lanes by the xor butterfly, wavefronts in index order
-__device__ double block_sum(double v, double* scratch)
-{
-    const int tid = threadIdx.x;
-    v = wave_sum(v);
-    __syncthreads();
-    if (tid % kWave == 0) scratch[tid / kWave] = v;
-    __syncthreads();
-    double total = 0.0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) total += scratch[w];
-    return total;
 }
 
 // The permutation with index p in [0, N!) as N nibbles (atom n -> site): p's mixed-radix digits are the Lehmer code c_n in

@@ -2359,12 +2359,12 @@ int mdx_atom_types_update(const float* logits, const int64_t* atom_types, const 
     return launch_pc(a, as_stream(stream));
 }
 
-int mdx_pc_step_update(const mdx_schedule_t* sched_host, int mode, int index_i, const int32_t* d_index,
-                       const mdx_pc_flags_t* f, const int64_t* atom_types, const float* x, const float* l,
-                       const float* logits, const float* score_x, const float* score_l, const float* z_coordinates,
-                       const float* gumbel, const float* u, const float* z_lattice, mdx_rng_t rng, int64_t batch,
-                       int number_of_atoms, int spatial_dimension, int64_t* atom_types_out, float* x_out, float* l_out,
-                       uint32_t* status, mdx_stream_t stream)
+// What mdx_pc_step_update and mdx_adaptive_corrector_update check first and fill alike.  MDX_OK with batch == 0: nothing to do;
+// the callers' own pointer checks and the 32-bit item check come after it, in each entry point's order.
+static int pc_common_args(const mdx_schedule_t* sched_host, int mode, int index_i, const int32_t* d_index, const mdx_pc_flags_t* f,
+                          const int64_t* atom_types, const float* logits, const float* gumbel, const float* u, mdx_rng_t rng,
+                          int64_t batch, int number_of_atoms, int spatial_dimension, int64_t* atom_types_out, uint32_t* status,
+                          PcArgs& a)
 {
     const int rc = check_index(sched_host, mode, index_i, d_index);
     if (rc != MDX_OK) return rc;
@@ -2372,27 +2372,41 @@ int mdx_pc_step_update(const mdx_schedule_t* sched_host, int mode, int index_i, 
     const int C = sched_host->num_classes;
     if (C < 2) return MDX_ERR_INVALID_ARG;
     if (C > MDX_MAX_CLASSES) return MDX_ERR_UNSUPPORTED;
-    if (batch == 0) return MDX_OK;
-    if (!x || !score_x || !x_out || !l || !l_out) return MDX_ERR_INVALID_ARG;
-    if (f->update_atom_types && (!atom_types || !logits || !atom_types_out)) return MDX_ERR_INVALID_ARG;
-    if (!f->use_fixed_lattice_parameters && !score_l) return MDX_ERR_INVALID_ARG;
-    if ((int64_t)batch * number_of_atoms > 0xffffffffLL) return MDX_ERR_UNSUPPORTED;   // 32-bit Philox item index
-    PcArgs a{};
     a.sched = to_dev(sched_host);
     a.use_tables = 1;
     a.mode = mode; a.index_i = index_i; a.d_index = d_index;
     a.atoms_pow = pow((double)number_of_atoms, 1.0 / (double)spatial_dimension);
     a.greedy = f->atom_type_greedy_sampling; a.one_transition = f->one_atom_type_transition_per_step;
-    a.fixed_lattice = f->use_fixed_lattice_parameters; a.update_types = f->update_atom_types;
-    a.do_coords = 1; a.do_lattice = 1;
+    a.fixed_lattice = f->use_fixed_lattice_parameters;
     a.small_eps = f->small_epsilon;
-    a.a = atom_types; a.x = x; a.l = l; a.logits = logits; a.score_x = score_x; a.score_l = score_l;
-    a.z_coord = z_coordinates; a.gumbel = gumbel; a.u = u; a.z_lat = z_lattice;
+    a.a = atom_types; a.logits = logits; a.gumbel = gumbel; a.u = u;
     a.rng = rng;
     a.B = batch; a.N = number_of_atoms; a.d = spatial_dimension; a.C = C;
     a.nl = spatial_dimension * (spatial_dimension + 1) / 2;
-    a.a_out = atom_types_out; a.x_out = x_out; a.l_out = l_out; a.p_out = nullptr;
+    a.a_out = atom_types_out; a.p_out = nullptr;
     a.status = status;
+    return MDX_OK;
+}
+
+int mdx_pc_step_update(const mdx_schedule_t* sched_host, int mode, int index_i, const int32_t* d_index,
+                       const mdx_pc_flags_t* f, const int64_t* atom_types, const float* x, const float* l,
+                       const float* logits, const float* score_x, const float* score_l, const float* z_coordinates,
+                       const float* gumbel, const float* u, const float* z_lattice, mdx_rng_t rng, int64_t batch,
+                       int number_of_atoms, int spatial_dimension, int64_t* atom_types_out, float* x_out, float* l_out,
+                       uint32_t* status, mdx_stream_t stream)
+{
+    PcArgs a{};
+    const int rc = pc_common_args(sched_host, mode, index_i, d_index, f, atom_types, logits, gumbel, u, rng, batch, number_of_atoms,
+                                  spatial_dimension, atom_types_out, status, a);
+    if (rc != MDX_OK || batch == 0) return rc;
+    if (!x || !score_x || !x_out || !l || !l_out) return MDX_ERR_INVALID_ARG;
+    if (f->update_atom_types && (!atom_types || !logits || !atom_types_out)) return MDX_ERR_INVALID_ARG;
+    if (!f->use_fixed_lattice_parameters && !score_l) return MDX_ERR_INVALID_ARG;
+    if ((int64_t)batch * number_of_atoms > 0xffffffffLL) return MDX_ERR_UNSUPPORTED;   // 32-bit Philox item index
+    a.update_types = f->update_atom_types;
+    a.do_coords = 1; a.do_lattice = 1;
+    a.x = x; a.l = l; a.score_x = score_x; a.score_l = score_l; a.z_coord = z_coordinates; a.z_lat = z_lattice;
+    a.x_out = x_out; a.l_out = l_out;
     return launch_pc(a, as_stream(stream));
 }
 
@@ -2460,13 +2474,10 @@ int mdx_adaptive_corrector_update(const mdx_schedule_t* sched_host, int mode, in
                                   mdx_rng_t rng, int64_t batch, int number_of_atoms, int spatial_dimension,
                                   int64_t* atom_types_out, float* x_out, float* l_out, uint32_t* status, mdx_stream_t stream)
 {
-    const int rc = check_index(sched_host, mode, index_i, d_index);
-    if (rc != MDX_OK) return rc;
-    if (!f || batch < 0 || number_of_atoms < 1 || spatial_dimension < 1 || spatial_dimension > 3) return MDX_ERR_INVALID_ARG;
-    const int C = sched_host->num_classes;
-    if (C < 2) return MDX_ERR_INVALID_ARG;
-    if (C > MDX_MAX_CLASSES) return MDX_ERR_UNSUPPORTED;
-    if (batch == 0) return MDX_OK;
+    PcArgs a{};
+    const int rc = pc_common_args(sched_host, mode, index_i, d_index, f, atom_types, logits, gumbel, u, rng, batch, number_of_atoms,
+                                  spatial_dimension, atom_types_out, status, a);
+    if (rc != MDX_OK || batch == 0) return rc;
     const int types = mode == MDX_PREDICTOR ? 1 : f->update_atom_types;
     if (types && (!atom_types || !logits || !atom_types_out)) return MDX_ERR_INVALID_ARG;
     if (mode == MDX_CORRECTOR) {
@@ -2474,24 +2485,11 @@ int mdx_adaptive_corrector_update(const mdx_schedule_t* sched_host, int mode, in
         if (!f->use_fixed_lattice_parameters && !score_l) return MDX_ERR_INVALID_ARG;
     }
     if ((int64_t)batch * number_of_atoms > 0xffffffffLL) return MDX_ERR_UNSUPPORTED;   // 32-bit Philox item index
-    PcArgs a{};
-    a.sched = to_dev(sched_host);
-    a.use_tables = 1;
-    a.mode = mode; a.index_i = index_i; a.d_index = d_index;
-    a.atoms_pow = pow((double)number_of_atoms, 1.0 / (double)spatial_dimension);
-    a.greedy = f->atom_type_greedy_sampling; a.one_transition = f->one_atom_type_transition_per_step;
-    a.fixed_lattice = f->use_fixed_lattice_parameters; a.update_types = types;
-    a.small_eps = f->small_epsilon;
-    a.a = atom_types; a.logits = logits; a.gumbel = gumbel; a.u = u;
+    a.update_types = types;
     if (mode == MDX_CORRECTOR) {     // (the predictor passes X and L through: it reads and writes neither)
         a.x = x; a.l = l; a.score_x = score_x; a.score_l = score_l; a.z_coord = z_coordinates; a.z_lat = z_lattice;
         a.x_out = x_out; a.l_out = l_out;
     }
-    a.rng = rng;
-    a.B = batch; a.N = number_of_atoms; a.d = spatial_dimension; a.C = C;
-    a.nl = spatial_dimension * (spatial_dimension + 1) / 2;
-    a.a_out = atom_types_out; a.p_out = nullptr;
-    a.status = status;
     return launch_adaptive_update(a, weights, as_stream(stream));
 }
 
@@ -2505,28 +2503,29 @@ int mdx_noise_relative_coordinates(const float* x0, const float* z, float sigma,
     return launch_status();
 }
 
-int mdx_noise_atom_types(const int64_t* a0, const float* q_bar, const float* u, int64_t n_atoms, int num_classes,
-                         int64_t* out, mdx_stream_t stream)
+// q_bar_stride: 0 for one [C, C] table shared by every atom, C * C for a table per atom
+static int noise_atom_types(const int64_t* a0, const float* q_bar, int64_t q_bar_stride, const float* u, int64_t n_atoms,
+                            int num_classes, int64_t* out, mdx_stream_t stream)
 {
     if (n_atoms < 0 || num_classes < 2) return MDX_ERR_INVALID_ARG;
     if (num_classes > MDX_MAX_CLASSES) return MDX_ERR_UNSUPPORTED;
     if (n_atoms == 0) return MDX_OK;
     if (!a0 || !q_bar || !u || !out) return MDX_ERR_INVALID_ARG;
     hipLaunchKernelGGL(noise_atom_types_kernel, dim3(flat_grid(n_atoms)), dim3(kBlock), 0, as_stream(stream), a0, q_bar,
-                       (int64_t)0, u, n_atoms, num_classes, out);
+                       q_bar_stride, u, n_atoms, num_classes, out);
     return launch_status();
+}
+
+int mdx_noise_atom_types(const int64_t* a0, const float* q_bar, const float* u, int64_t n_atoms, int num_classes,
+                         int64_t* out, mdx_stream_t stream)
+{
+    return noise_atom_types(a0, q_bar, 0, u, n_atoms, num_classes, out, stream);
 }
 
 int mdx_noise_atom_types_per_atom(const int64_t* a0, const float* q_bar, const float* u, int64_t n_atoms, int num_classes,
                                   int64_t* out, mdx_stream_t stream)
 {
-    if (n_atoms < 0 || num_classes < 2) return MDX_ERR_INVALID_ARG;
-    if (num_classes > MDX_MAX_CLASSES) return MDX_ERR_UNSUPPORTED;
-    if (n_atoms == 0) return MDX_OK;
-    if (!a0 || !q_bar || !u || !out) return MDX_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(noise_atom_types_kernel, dim3(flat_grid(n_atoms)), dim3(kBlock), 0, as_stream(stream), a0, q_bar,
-                       (int64_t)num_classes * num_classes, u, n_atoms, num_classes, out);
-    return launch_status();
+    return noise_atom_types(a0, q_bar, (int64_t)num_classes * num_classes, u, n_atoms, num_classes, out, stream);
 }
 
 int mdx_noise_relative_coordinates_sigmas(const float* x0, const float* z, const float* sigmas, int64_t count, float* out,
@@ -2549,25 +2548,38 @@ int mdx_noise_lattice_parameters(const float* l0, const float* z, const float* s
     return launch_status();
 }
 
+// What the two repaint entry points check first and fill alike; K: the constrained rows per structure (their number, or the
+// capacity of an environment).  "Nothing to do" and the pointer checks come after it, in the callers.
+static int repaint_common_args(const mdx_schedule_t* sched_host, int index_i, const int32_t* d_index, const float* constrained_x,
+                               const int64_t* constrained_a, const int64_t* constrained_indices, int K, const float* z,
+                               const float* u, mdx_rng_t rng, int64_t batch, int number_of_atoms, int spatial_dimension,
+                               float* x_inout, int64_t* a_inout, RepaintArgs& a)
+{
+    if (!sched_host || batch < 0 || K < 0 || number_of_atoms < 1) return MDX_ERR_INVALID_ARG;
+    if (spatial_dimension < 1 || spatial_dimension > 3 || K > number_of_atoms) return MDX_ERR_INVALID_ARG;
+    if (!d_index && (index_i < 0 || index_i > sched_host->total_time_steps)) return MDX_ERR_INVALID_ARG;
+    if (sched_host->num_classes > MDX_MAX_CLASSES) return MDX_ERR_UNSUPPORTED;
+    a.sched = to_dev(sched_host);
+    a.index_i = index_i; a.d_index = d_index;
+    a.cx = constrained_x; a.ca = constrained_a; a.cidx = constrained_indices; a.K = K;
+    a.z = z; a.u = u; a.rng = rng;
+    a.B = batch; a.N = number_of_atoms; a.d = spatial_dimension; a.C = sched_host->num_classes;
+    a.x = x_inout; a.a = a_inout;
+    return MDX_OK;
+}
+
 int mdx_repaint_constrained_rows(const mdx_schedule_t* sched_host, int index_i, const int32_t* d_index,
                                  const float* constrained_x, const int64_t* constrained_a,
                                  const int64_t* constrained_indices, int number_of_constraints, const float* z,
                                  const float* u, mdx_rng_t rng, int64_t batch, int number_of_atoms,
                                  int spatial_dimension, float* x_inout, int64_t* a_inout, mdx_stream_t stream)
 {
-    if (!sched_host || batch < 0 || number_of_constraints < 0 || number_of_atoms < 1) return MDX_ERR_INVALID_ARG;
-    if (spatial_dimension < 1 || spatial_dimension > 3 || number_of_constraints > number_of_atoms) return MDX_ERR_INVALID_ARG;
-    if (!d_index && (index_i < 0 || index_i > sched_host->total_time_steps)) return MDX_ERR_INVALID_ARG;
-    if (sched_host->num_classes > MDX_MAX_CLASSES) return MDX_ERR_UNSUPPORTED;
+    RepaintArgs a{};
+    const int rc = repaint_common_args(sched_host, index_i, d_index, constrained_x, constrained_a, constrained_indices,
+                                       number_of_constraints, z, u, rng, batch, number_of_atoms, spatial_dimension, x_inout, a_inout, a);
+    if (rc != MDX_OK) return rc;
     if (batch == 0 || number_of_constraints == 0) return MDX_OK;
     if (!constrained_x || !constrained_a || !constrained_indices || !x_inout || !a_inout) return MDX_ERR_INVALID_ARG;
-    RepaintArgs a{};
-    a.sched = to_dev(sched_host);
-    a.index_i = index_i; a.d_index = d_index;
-    a.cx = constrained_x; a.ca = constrained_a; a.cidx = constrained_indices; a.K = number_of_constraints;
-    a.z = z; a.u = u; a.rng = rng;
-    a.B = batch; a.N = number_of_atoms; a.d = spatial_dimension; a.C = sched_host->num_classes;
-    a.x = x_inout; a.a = a_inout;
     hipLaunchKernelGGL(repaint_rows_kernel, dim3(flat_grid(batch * number_of_constraints)), dim3(kBlock), 0,
                        as_stream(stream), a);
     return launch_status();
@@ -2579,20 +2591,14 @@ int mdx_repaint_rows_per_sample(const mdx_schedule_t* sched_host, int index_i, c
                                 const int32_t* sample_environment, const float* z, const float* u, mdx_rng_t rng, int64_t batch,
                                 int number_of_atoms, int spatial_dimension, float* x_inout, int64_t* a_inout, mdx_stream_t stream)
 {
-    if (!sched_host || batch < 0 || number_of_environments < 0 || capacity < 0 || number_of_atoms < 1) return MDX_ERR_INVALID_ARG;
-    if (spatial_dimension < 1 || spatial_dimension > 3 || capacity > number_of_atoms) return MDX_ERR_INVALID_ARG;
-    if (!d_index && (index_i < 0 || index_i > sched_host->total_time_steps)) return MDX_ERR_INVALID_ARG;
-    if (sched_host->num_classes > MDX_MAX_CLASSES) return MDX_ERR_UNSUPPORTED;
+    if (number_of_environments < 0) return MDX_ERR_INVALID_ARG;
+    RepaintArgs a{};
+    const int rc = repaint_common_args(sched_host, index_i, d_index, constrained_x, constrained_a, constrained_indices, capacity, z,
+                                       u, rng, batch, number_of_atoms, spatial_dimension, x_inout, a_inout, a);
+    if (rc != MDX_OK) return rc;
     if (batch == 0 || capacity == 0 || number_of_environments == 0) return MDX_OK;
     if (!constrained_x || !constrained_a || !constrained_indices || !counts || !sample_environment || !x_inout || !a_inout)
         return MDX_ERR_INVALID_ARG;
-    RepaintArgs a{};
-    a.sched = to_dev(sched_host);
-    a.index_i = index_i; a.d_index = d_index;
-    a.cx = constrained_x; a.ca = constrained_a; a.cidx = constrained_indices; a.K = capacity;
-    a.z = z; a.u = u; a.rng = rng;
-    a.B = batch; a.N = number_of_atoms; a.d = spatial_dimension; a.C = sched_host->num_classes;
-    a.x = x_inout; a.a = a_inout;
     hipLaunchKernelGGL(repaint_rows_per_sample_kernel, dim3(flat_grid(batch * capacity)), dim3(kBlock), 0, as_stream(stream), a,
                        sample_environment, counts, number_of_environments);
     return launch_status();

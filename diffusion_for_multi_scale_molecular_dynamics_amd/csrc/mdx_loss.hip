@@ -20,6 +20,7 @@
 
 #include "../../include/mdx_hip.h"
 #include "mdx_launch.hpp"
+#include "mdx_reduce.hpp"
 #include "mdx_wrapped_score.hpp"
 
 using namespace mdx;
@@ -52,9 +53,6 @@ struct LossArgs {
     float *target_x, *target_l, *loss_x, *loss_a, *loss_l, *per_structure, *q_atm1, *p_atm1, *vb_term, *ce_term;
     uint32_t* status;
 };
-
-__device__ __forceinline__ bool finite_(double v) { return __builtin_fabs(v) < 1.0e300; }
-__device__ __forceinline__ bool sigma_valid(double s) { return s > 0.0 && finite_(s); }
 
 // torch.clip(min=floor): a NaN stays a NaN
 __device__ __forceinline__ double clip_min(double v, double floor_value) { return v < floor_value ? floor_value : v; }

@@ -23,6 +23,7 @@
 
 #include "../../include/mdx_hip.h"
 #include "mdx_launch.hpp"
+#include "mdx_reduce.hpp"
 
 using namespace mdx;
 
@@ -32,15 +33,6 @@ constexpr int kMaxAtoms = 256;                // the transport unit's limits
 constexpr int kMaxDimension = 3;
 constexpr double kTauMin = -0.5, kTauMax = 0.5;      // TAU_RANGE_MIN, TAU_RANGE_MAX
 constexpr int kNoPlateau = 0x7fffffff;
-
-__device__ __forceinline__ bool finite_(double v) { return __builtin_fabs(v) < 1.0e300; }
-
-__device__ __forceinline__ int wave_sum_int(int v)
-{
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
 
 __global__ __launch_bounds__(kMaxAtoms) void optimal_translation_kernel(const float* __restrict__ x, int64_t x_stride,
                                                                         const float* __restrict__ y, int N, int D,
@@ -173,7 +165,7 @@ __global__ __launch_bounds__(kMaxAtoms) void optimal_translation_kernel(const fl
         best = take ? other : best;
         best_k = take ? other_k : best_k;
     }
-    count = wave_sum_int(count);
+    count = wave_sum(count);
     if (lane == 0) {
         const bool found = best_k <= N;
         tau[out] = found ? (float)rhs[best_k] : __builtin_huge_valf();

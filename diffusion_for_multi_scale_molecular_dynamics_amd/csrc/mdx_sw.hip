@@ -1,7 +1,8 @@
 // Stillinger-Weber energies and forces of a batch of periodic structures (LAMMPS `pair_style sw`, metal units): what the
 // reference's energy oracle asks LAMMPS for (oracle/lammps_energy_oracle.py:56-158 through energy_oracle.py:44-131), as a closed
-// formula over the periodic pair test of radius_graph_kernel / force_field_kernel (their staging and 27-image sweep, re-stated
-// here in binary64).  See include/mdx_hip.h (mdx_stillinger_weber_energy_forces) for the contract.
+// formula over a periodic pair test like that of radius_graph_kernel / force_field_kernel.  The staging and the 27-image sweep
+// here are other arithmetic, not a copy of theirs: binary64 positions from the raw sides, a cutoff per pair of types, three
+// nested loops that leave an axis early.  See include/mdx_hip.h (mdx_stillinger_weber_energy_forces) for the contract.
 //
 //   stillinger_weber_kernel    one workgroup per structure, three phases separated by workgroup barriers:
 //     0  stage: position = (double)relative * (double)side, atom types, the pair cutoffs a*sigma of the (ti,tj,tj) entries;
@@ -19,6 +20,7 @@
 
 #include "../../include/mdx_hip.h"
 #include "mdx_launch.hpp"
+#include "mdx_reduce.hpp"
 
 using namespace mdx;
 
@@ -110,7 +112,7 @@ __global__ __launch_bounds__(kBlock) void stillinger_weber_kernel(const float* _
         for (int k = 0; k < 3; ++k) {
             const double p = (double)relative[(b * N + i) * 3 + k] * side[k];
             pos[3 * i + k] = p;
-            if (!(__builtin_fabs(p) < 1.0e300)) bad |= kNotFinite;
+            if (!finite_(p)) bad |= kNotFinite;
         }
         if (bad) atomicOr(&flags, bad);
     }

@@ -25,6 +25,7 @@
 #include "../../include/mdx_hip.h"
 #include "mdx_launch.hpp"
 #include "mdx_math.hpp"
+#include "mdx_reduce.hpp"
 #include "mdx_wrapped_score.hpp"
 
 using namespace mdx;
@@ -40,9 +41,6 @@ constexpr int kRawWaves = kBlock / kWave;
 constexpr int kNoColumn = 0x7fffffff;
 constexpr int kBadSigma = 1, kBadCoordinate = 2;
 constexpr double kTwoPi = 2.0 * kPi;
-
-__device__ __forceinline__ bool finite_(double v) { return __builtin_fabs(v) < 1.0e300; }
-__device__ __forceinline__ bool sigma_valid(double s) { return s > 0.0 && finite_(s); }
 
 // LDS written by some lanes of this wavefront is read by others after this point
 __device__ __forceinline__ void wave_sync()

@@ -527,13 +527,17 @@ def raise_analytical_bits(word: int):
         raise AssertionError("the relative coordinates should all be in [0, 1)")
 
 
+def _take_status_bits(status: torch.Tensor, mask: int) -> int:
+    """The status word, by one host read; the bits of `mask` that were set in it are cleared (the other kernels' stay)."""
+    word = int(status.item())
+    if word & mask:
+        status.bitwise_and_(~mask)
+    return word
+
+
 def raise_analytical_status(status: torch.Tensor):
     """One host read of a status word the analytical kernels reported into: their bits are cleared, then raised."""
-    both = _hip.STATUS_ANALYTICAL_SIGMA | _hip.STATUS_ANALYTICAL_COORDINATES
-    word = int(status.item())
-    if word & both:
-        status.bitwise_and_(~both)
-    raise_analytical_bits(word)
+    raise_analytical_bits(_take_status_bits(status, _hip.STATUS_ANALYTICAL_SIGMA | _hip.STATUS_ANALYTICAL_COORDINATES))
 
 
 def wrapped_gaussian_sigma_normalized_score(relative_coordinates, sigmas, kmax: int, coordinates_bounded: bool = True,
@@ -710,10 +714,8 @@ def root_of_atom_count(number_of_atoms: int, degree: int) -> float:
 def raise_loss_status(status: torch.Tensor):
     """One host read of a status word mdx_denoising_loss reported into: its bits are cleared, then raised -- the reference's
     value assertion on the logits (utils/d3pm_utils.py:144-145), the wrapped score's two, and an index outside its table."""
-    own = _hip.STATUS_LOSS_LOGITS | _hip.STATUS_LOSS_INDEX | _hip.STATUS_ANALYTICAL_SIGMA | _hip.STATUS_ANALYTICAL_COORDINATES
-    word = int(status.item())
-    if word & own:
-        status.bitwise_and_(~own)
+    word = _take_status_bits(status, _hip.STATUS_LOSS_LOGITS | _hip.STATUS_LOSS_INDEX | _hip.STATUS_ANALYTICAL_SIGMA |
+                             _hip.STATUS_ANALYTICAL_COORDINATES)
     if word & _hip.STATUS_LOSS_LOGITS:
         raise AssertionError(LOSS_LOGITS_MESSAGE)
     if word & _hip.STATUS_LOSS_INDEX:

@@ -21,6 +21,7 @@ from ...namespace import AXL, NOISE, NOISY_AXL_COMPOSITION
 from ...score.wrapped_gaussian_score import get_coordinates_sigma_normalized_score, get_log_wrapped_gaussians
 from ...utils.basis_transformations import map_relative_coordinates_to_unit_cell
 from ...utils.symmetry_utils import get_all_permutation_indices
+from ._exact_score_outputs import _ExactScoreOutputs
 from .score_network import ScoreNetwork, ScoreNetworkParameters
 
 
@@ -45,8 +46,10 @@ class AnalyticalScoreNetworkParameters(ScoreNetworkParameters):
                 "The equilibrium coordinates should be consistent with the spatial dimension."
 
 
-class AnalyticalScoreNetwork(ScoreNetwork):
+class AnalyticalScoreNetwork(_ExactScoreOutputs, ScoreNetwork):
     """Score network based on analytical integration of Gaussian distributions."""
+
+    _device_copies_slot = "_sites_on"
 
     def __init__(self, hyper_params: AnalyticalScoreNetworkParameters):
         super().__init__(hyper_params)
@@ -81,28 +84,6 @@ class AnalyticalScoreNetwork(ScoreNetwork):
         perm_indices, _ = get_all_permutation_indices(relative_coordinates.shape[0])
         return relative_coordinates[perm_indices]
 
-    # ---- what the samplers look for (generators/network_hooks.py)
-    def capture_safe(self, batch_size: int, number_of_atoms: int, device) -> bool:
-        """No host read in the forward: the forward can always be captured into a hipGraph."""
-        return True
-
-    def check_status(self):
-        """One host read of the status word: the reference's assertion for an invalid sigma or coordinate; the word is cleared."""
-        if self.graph_status is not None:
-            kernels.raise_analytical_status(self.graph_status)
-
-    def _status_on(self, device) -> torch.Tensor:
-        if self.graph_status is None or self.graph_status.device != device:
-            self.graph_status = torch.zeros(1, dtype=torch.int32, device=device)
-        return self.graph_status
-
-    def _sites(self, device) -> torch.Tensor:
-        """Row 0 of all_x0 on `device`, copied there once (a forward inside a captured loop must not upload)."""
-        key = (device, self.all_x0.data_ptr(), self.all_x0._version)
-        if self._sites_on is None or self._sites_on[0] != key:
-            self._sites_on = (key, self.all_x0[0].detach().to(device=device, dtype=torch.float32).contiguous())
-        return self._sites_on[1]
-
     def get_log_wrapped_gaussians_and_normalized_scores_centered_on_equilibrium_positions(
             self, relative_coordinates: torch.tensor, sigmas_t: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """(log wrapped Gaussians [P, batch], sigma-normalised scores [P, batch, natoms, d]) centred on each of the P rows of
@@ -131,15 +112,10 @@ class AnalyticalScoreNetwork(ScoreNetwork):
         status = torch.zeros(1, dtype=torch.int32, device=relative_coordinates.device) if relative_coordinates.is_cuda else None
         scores, probabilities = kernels.analytical_score(
             relative_coordinates.to(torch.float32).contiguous(), sigmas_t.to(torch.float32).contiguous(),
-            self._sites(relative_coordinates.device), self.sigma_d_square, self.kmax, self.use_permutation_invariance,
+            *self._copies_on(relative_coordinates.device, self.all_x0[0]), self.sigma_d_square, self.kmax, self.use_permutation_invariance,
             with_probabilities=True, status=status)
         kernels.raise_analytical_status(status)
         return probabilities, scores
-
-    def _check_batch(self, batch: Dict[AnyStr, torch.Tensor]):
-        super()._check_batch(batch)
-        assert batch[NOISY_AXL_COMPOSITION].X.shape[1] == self.natoms, \
-            "The dimension corresponding to the number of atoms is not consistent with the configuration."
 
     def _forward_unchecked(self, batch: Dict[AnyStr, Any], conditional: bool = False) -> AXL:
         """AXL(A = logits (0, .., 0, -inf): one possible atom type, X = the analytical score, L = zeros in the reference's
@@ -149,18 +125,6 @@ class AnalyticalScoreNetwork(ScoreNetwork):
         sigmas = batch[NOISE].to(xt.device)         # [batch_size, 1]
         batch_size = xt.shape[0]
         scores, _ = kernels.analytical_score(xt.to(torch.float32).contiguous(), sigmas.to(torch.float32).contiguous(),
-                                             self._sites(xt.device), self.sigma_d_square, self.kmax,
+                                             *self._copies_on(xt.device, self.all_x0[0]), self.sigma_d_square, self.kmax,
                                              self.use_permutation_invariance, status=self._status_on(xt.device) if xt.is_cuda else None)
-        atomic_logits, zeros = self._constant_outputs(batch_size, xt.device)
-        return AXL(A=atomic_logits, X=scores, L=zeros)
-
-    def _constant_outputs(self, batch_size: int, device):
-        """The logits (0, .., 0, -inf) [batch, natoms, classes] and the zero lattice output [batch, natoms, d]: constants, made
-        once per (batch size, device) and returned by every forward (read-only by contract: the samplers only read them), so
-        that a forward inside the loop is the kernel and nothing else of this class's."""
-        key = (batch_size, device)
-        if self._constants is None or self._constants[0] != key:
-            atomic_logits = torch.zeros(batch_size, self.natoms, self.number_of_atomic_classes, device=device)
-            atomic_logits[..., -1] = -torch.inf
-            self._constants = (key, atomic_logits, torch.zeros(batch_size, self.natoms, self.spatial_dimension, device=device))
-        return self._constants[1], self._constants[2]
+        return self._as_axl(scores, batch_size, xt.device)

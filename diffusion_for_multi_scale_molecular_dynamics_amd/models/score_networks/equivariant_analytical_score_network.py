@@ -20,6 +20,7 @@ from ...score.wrapped_gaussian_score import get_coordinates_sigma_normalized_sco
 from ...transport.transporter import Transporter
 from ...utils.basis_transformations import map_relative_coordinates_to_unit_cell
 from ...utils.geometric_utils import get_cubic_point_group_symmetries
+from ._exact_score_outputs import _ExactScoreOutputs
 from .score_network import ScoreNetwork, ScoreNetworkParameters
 
 
@@ -44,8 +45,10 @@ class EquivariantAnalyticalScoreNetworkParameters(ScoreNetworkParameters):
                 "The equilibrium coordinates should be consistent with the spatial dimension."
 
 
-class EquivariantAnalyticalScoreNetwork(ScoreNetwork):
+class EquivariantAnalyticalScoreNetwork(_ExactScoreOutputs, ScoreNetwork):
     """Score network based on analytical integration of Gaussian distributions, equivariant by optimal transport."""
+
+    _device_copies_slot = "_on_device"
 
     def __init__(self, hyper_params: EquivariantAnalyticalScoreNetworkParameters):
         super().__init__(hyper_params)
@@ -71,35 +74,11 @@ class EquivariantAnalyticalScoreNetwork(ScoreNetwork):
         self._constants = None
         self.graph_status = None        # int32 [1] on the inputs' device, made by the first forward (generators/network_hooks.py)
 
-    # ---- what the samplers look for (generators/network_hooks.py)
-    def capture_safe(self, batch_size: int, number_of_atoms: int, device) -> bool:
-        """No host read in the forward: the forward can always be captured into a hipGraph."""
-        return True
-
-    def check_status(self):
-        """One host read of the status word: the reference's assertion for an invalid sigma or coordinate; the word is cleared."""
-        if self.graph_status is not None:
-            kernels.raise_analytical_status(self.graph_status)
-
-    def _status_on(self, device) -> torch.Tensor:
-        if self.graph_status is None or self.graph_status.device != device:
-            self.graph_status = torch.zeros(1, dtype=torch.int32, device=device)
-        return self.graph_status
-
-    def _sites_and_symmetries(self, device):
-        """The two parameters as f32 on `device`, copied there once (a forward inside a captured loop must not upload)."""
-        sites, symmetries = self.equilibrium_relative_coordinates, self.symmetries
-        key = (device, sites.data_ptr(), sites._version, symmetries.data_ptr(), symmetries._version)
-        if self._on_device is None or self._on_device[0] != key:
-            self._on_device = (key, sites.detach().to(device=device, dtype=torch.float32).contiguous(),
-                               symmetries.detach().to(device=device, dtype=torch.float32).contiguous())
-        return self._on_device[1], self._on_device[2]
-
     def get_nearest_equilibrium_coordinates(self, relative_coordinates: torch.Tensor) -> torch.Tensor:
         """The symmetry-group image of the equilibrium coordinates aligned with each structure of relative_coordinates
         [batch_size, num_atoms, spatial_dimension]: same shape (:93-107).  One kernel; the sites are shared, not repeated."""
-        sites, symmetries = self._sites_and_symmetries(relative_coordinates.device)
-        return kernels.transport_align(relative_coordinates.to(torch.float32).contiguous(), sites, symmetries)
+        return kernels.transport_align(relative_coordinates.to(torch.float32).contiguous(),
+                                       *self._copies_on(relative_coordinates.device, self.equilibrium_relative_coordinates, self.symmetries))
 
     def _get_jacobian_matrix(self, x: torch.Tensor) -> torch.Tensor:
         """J_ij = d c_j / d x_i of the translation-invariant coordinates c(x), diagonal in the spatial index:
@@ -131,30 +110,14 @@ class EquivariantAnalyticalScoreNetwork(ScoreNetwork):
         effective_sigma_normalized_scores = get_coordinates_sigma_normalized_score(u, effective_sigmas, self.kmax)
         return sigmas_t * effective_sigma_normalized_scores / effective_sigmas
 
-    def _check_batch(self, batch: Dict[AnyStr, torch.Tensor]):
-        super()._check_batch(batch)
-        assert batch[NOISY_AXL_COMPOSITION].X.shape[1] == self.natoms, \
-            "The dimension corresponding to the number of atoms is not consistent with the configuration."
-
     def _forward_unchecked(self, batch: Dict[AnyStr, Any], conditional: bool = False) -> AXL:
         """AXL(A = logits (0, .., 0, -inf): one possible atom type, X = the score, L = zeros [batch, natoms, d]) (:195-241),
         all on the inputs' device.  `conditional` does nothing, as in the reference.  Invalid inputs do not raise here (no host
         read): their structures hold NaNs and check_status() reports them."""
         xt = batch[NOISY_AXL_COMPOSITION].X
         sigmas = batch[NOISE].to(xt.device)         # [batch_size, 1]
-        sites, symmetries = self._sites_and_symmetries(xt.device)
+        sites, symmetries = self._copies_on(xt.device, self.equilibrium_relative_coordinates, self.symmetries)
         scores = kernels.equivariant_analytical_score(xt.to(torch.float32).contiguous(), sigmas.to(torch.float32).contiguous(),
                                                       sites, symmetries, self.sigma_d_square, self.kmax,
                                                       status=self._status_on(xt.device) if xt.is_cuda else None)
-        atomic_logits, zeros = self._constant_outputs(xt.shape[0], xt.device)
-        return AXL(A=atomic_logits, X=scores, L=zeros)
-
-    def _constant_outputs(self, batch_size: int, device):
-        """The logits (0, .., 0, -inf) [batch, natoms, classes] and the zero lattice output [batch, natoms, d]: constants, made
-        once per (batch size, device) and returned by every forward (read-only by contract), as AnalyticalScoreNetwork's."""
-        key = (batch_size, device)
-        if self._constants is None or self._constants[0] != key:
-            atomic_logits = torch.zeros(batch_size, self.natoms, self.number_of_atomic_classes, device=device)
-            atomic_logits[..., -1] = -torch.inf
-            self._constants = (key, atomic_logits, torch.zeros(batch_size, self.natoms, self.spatial_dimension, device=device))
-        return self._constants[1], self._constants[2]
+        return self._as_axl(scores, xt.shape[0], xt.device)
