@@ -15,6 +15,8 @@
 // Binary64 throughout, from the binary32 inputs promoted once; every output value is rounded once.  No atomics in the
 // arithmetic, every sum in a fixed order: a launch or a hipGraph replay always gives the same bits.  The status word alone is
 // OR-ed atomically, as everywhere in this library.  64-wide wavefronts are assumed (gfx950).
+//
+// The consistency regularizer's target and loss (mdx_consistency_loss) are the second member of the family, further down.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -287,6 +289,93 @@ __global__ __launch_bounds__(kBlock) void denoising_loss_kernel(const LossArgs a
     if (bits && a.status) atomicOr(a.status, bits);
 }
 
+// ---- the consistency regularizer's target and loss (regularizers/consistency_regularizer.py:190-308; see include/mdx_hip.h)
+//
+//   consistency_loss_kernel     one workgroup per structure (64 .. 256 threads), element e = tid, tid + threads, ..
+//       u = wrap(x_start - x_end), sigma_eff = sqrt(sigma_start^2 - sigma_end^2),
+//       target = (sigma_start / sigma_eff) x [sigma_eff x score of the wrapped Gaussian at u], term = s (s - 2 target),
+//       gradient = 2 (s - target) / batch; the structure's sum of terms as denoising_loss_kernel forms its means
+//   consistency_total_kernel    one workgroup: the binary64 sums of the structures, added in structure order by thread 0, divided
+//                               by the batch
+struct ConsistencyArgs {
+    const float *x_start, *x_end, *score, *sigma_start, *sigma_end;
+    int sigma_stride, ND, kmax;
+    double batch;
+    float *target, *gradient, *per_structure;
+    double* structure_sums;
+    uint32_t* status;
+};
+
+__global__ __launch_bounds__(kBlock) void consistency_loss_kernel(const ConsistencyArgs a)
+{
+    __shared__ double partial[kMaxWaves];
+    const int tid = threadIdx.x, threads = blockDim.x, waves = threads / kWave, wave = tid / kWave, lane = tid % kWave;
+    const int64_t b = blockIdx.x;
+    const int ND = a.ND;
+    const double nan = __builtin_nan("");
+    uint32_t bits = 0;
+
+    // sigma_end = 0 is the end of a trajectory that reaches time index 0: valid
+    const double sigma_start = (double)a.sigma_start[b * a.sigma_stride], sigma_end = (double)a.sigma_end[b * a.sigma_stride];
+    const bool sigmas_valid = sigma_valid(sigma_start) && sigma_end >= 0.0 && finite_(sigma_end) && sigma_start > sigma_end;
+    const double sigma_effective = sigmas_valid ? sqrt(sigma_start * sigma_start - sigma_end * sigma_end) : nan;
+    const double ratio = sigma_start / sigma_effective;
+    if (!sigmas_valid) bits |= MDX_STATUS_ANALYTICAL_SIGMA;
+
+    double sum = 0.0;
+    for (int e = tid; e < ND; e += threads) {
+        const int64_t i = b * ND + e;
+        const double x_start = (double)a.x_start[i], x_end = (double)a.x_end[i];
+        double target;
+        if (!sigmas_valid) {
+            target = nan;
+        } else if (!finite_(x_start) || !finite_(x_end)) {
+            bits |= MDX_STATUS_ANALYTICAL_COORDINATES;
+            target = nan;
+        } else {
+            target = ratio * sigma_normalized_score(wrap01(x_start - x_end), sigma_effective, a.kmax);
+        }
+        store(a.target, i, target);
+        if (a.score) {
+            const double s = (double)a.score[i];
+            store(a.gradient, i, 2.0 * (s - target) / a.batch);
+            sum += s * (s - 2.0 * target);
+        }
+    }
+
+    if (a.score && (a.per_structure || a.structure_sums)) {
+        sum = wave_sum(sum);
+        if (lane == 0) partial[wave] = sum;
+        __syncthreads();
+        if (tid == 0) {
+            double total = 0.0;
+            for (int w = 0; w < waves; ++w) total += partial[w];
+            store(a.per_structure, b, total);
+            if (a.structure_sums) a.structure_sums[b] = total;
+        }
+    }
+    if (bits && a.status) atomicOr(a.status, bits);
+}
+
+// one workgroup of kBlock threads: the sums come through LDS kBlock at a time (one coalesced read, not one round trip to memory
+// per structure), thread 0 adds them in structure order
+__global__ __launch_bounds__(kBlock) void consistency_total_kernel(const double* structure_sums, int64_t batch, float* loss)
+{
+    __shared__ double chunk[kBlock];
+    const int tid = threadIdx.x;
+    double total = 0.0;
+    for (int64_t base = 0; base < batch; base += kBlock) {
+        if (base + tid < batch) chunk[tid] = structure_sums[base + tid];
+        __syncthreads();
+        if (tid == 0) {
+            const int count = batch - base < kBlock ? (int)(batch - base) : kBlock;
+            for (int k = 0; k < count; ++k) total += chunk[k];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) loss[0] = (float)(total / (double)batch);
+}
+
 }  // namespace
 
 extern "C" {
@@ -350,6 +439,33 @@ int mdx_denoising_loss(const float* x0, const float* xt, const float* target_x_i
     int64_t threads = cdiv((int64_t)N * D, kWave) * kWave;
     threads = threads > kBlock ? kBlock : threads;
     hipLaunchKernelGGL(denoising_loss_kernel, dim3((unsigned)batch), dim3((unsigned)threads), 0, as_stream(stream), a);
+    return launch_status();
+}
+
+int mdx_consistency_loss(const float* x_start, const float* x_end, const float* score, const float* sigma_start,
+                         const float* sigma_end, int sigma_stride, int64_t batch, int number_of_atoms, int spatial_dimension,
+                         int kmax, float* target, float* gradient, float* per_structure, double* structure_sums, float* loss,
+                         uint32_t* status, mdx_stream_t stream)
+{
+    const int N = number_of_atoms, D = spatial_dimension;
+    if (batch < 0 || N < 1 || D < 1 || kmax < 0 || (sigma_stride != 0 && sigma_stride != 1)) return MDX_ERR_INVALID_ARG;
+    if (N > kMaxAtoms || D > kMaxDimension || kmax > kMaxTranslation || batch > 0x7fffffffLL) return MDX_ERR_UNSUPPORTED;
+    if (!x_start || !x_end || !sigma_start || !sigma_end) return MDX_ERR_INVALID_ARG;
+    if (!score && (gradient || per_structure || structure_sums || loss)) return MDX_ERR_INVALID_ARG;
+    if (!score && !target) return MDX_ERR_INVALID_ARG;
+    if (loss && !structure_sums) return MDX_ERR_INVALID_ARG;
+    if (batch == 0) return MDX_OK;
+    ConsistencyArgs a;
+    a.x_start = x_start, a.x_end = x_end, a.score = score, a.sigma_start = sigma_start, a.sigma_end = sigma_end;
+    a.sigma_stride = sigma_stride, a.ND = N * D, a.kmax = kmax;
+    a.batch = (double)batch;
+    a.target = target, a.gradient = gradient, a.per_structure = per_structure, a.structure_sums = structure_sums;
+    a.status = status;
+    int64_t threads = cdiv((int64_t)N * D, kWave) * kWave;
+    threads = threads > kBlock ? kBlock : threads;
+    hipLaunchKernelGGL(consistency_loss_kernel, dim3((unsigned)batch), dim3((unsigned)threads), 0, as_stream(stream), a);
+    if (loss)
+        hipLaunchKernelGGL(consistency_total_kernel, dim3(1), dim3(kBlock), 0, as_stream(stream), structure_sums, batch, loss);
     return launch_status();
 }
 

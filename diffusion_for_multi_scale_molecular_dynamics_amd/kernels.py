@@ -819,6 +819,72 @@ def denoising_loss(*, x0=None, xt=None, target_x=None, predicted_x=None, sigma=N
     return out
 
 
+ConsistencyLoss = namedtuple("ConsistencyLoss", ["target", "gradient", "per_structure", "loss"])
+
+
+def _sigma_words(name: str, sigma, batch: int, device) -> torch.Tensor:
+    """A Python float or a 0-dim tensor as a one-element f32 device word; a tensor with 1 or `batch` elements as it is (flat)."""
+    if not isinstance(sigma, torch.Tensor):
+        return torch.full((1,), float(sigma), dtype=F32, device=device)
+    if sigma.numel() not in (1, batch):
+        raise ValueError(f"{name} has shape {tuple(sigma.shape)}: expected one value, or one per structure, [{batch}]")
+    return sigma.detach().to(dtype=F32).reshape(-1).contiguous()
+
+
+class _ConsistencyLossFunction(torch.autograd.Function):
+    """loss(score) of mdx_consistency_loss for a score that requires grad: backward is grad_output x the kernel's own gradient
+    buffer, 2 (s - target) / B, no second launch."""
+
+    @staticmethod
+    def forward(ctx, score, loss, gradient):
+        ctx.save_for_backward(gradient)
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        gradient, = ctx.saved_tensors
+        return grad_output * gradient, None, None
+
+
+def consistency_loss(x_start, x_end, score=None, *, sigma_start, sigma_end, kmax: int = 4,
+                     status: Optional[torch.Tensor] = None) -> ConsistencyLoss:
+    """The consistency regularizer's target and loss (mdx_consistency_loss), no host read: x_start, x_end, score f32 [B, N, D];
+    sigma_start, sigma_end a Python float, a 0-dim tensor, or a tensor with 1 or B elements (both alike).  Returns a
+    ConsistencyLoss of f32 tensors: target [B, N, D] = sigma_start x the score of the wrapped Gaussian of width
+    sqrt(sigma_start^2 - sigma_end^2) at wrap(x_start - x_end); gradient [B, N, D] = 2 (score - target) / B; per_structure [B],
+    the sums of score (score - 2 target); loss (0-dim), their sum over B.  Without `score` only target is made.  When `score`
+    requires grad, loss carries it: its backward returns grad_output x gradient.  An invalid sigma or coordinate gives NaNs
+    and its bit in `status` (raise_analytical_status)."""
+    _device_only("the consistency loss", x_start=x_start, x_end=x_end, score=score, status=status,
+                 sigma_start=sigma_start if isinstance(sigma_start, torch.Tensor) else None,
+                 sigma_end=sigma_end if isinstance(sigma_end, torch.Tensor) else None)
+    if x_start.dim() != 3:
+        raise ValueError(f"x_start has shape {tuple(x_start.shape)}, expected [B, N, D]")
+    B, N, D = x_start.shape
+    if B < 1:
+        raise ValueError("the consistency loss of an empty batch is not defined")
+    for name, t in (("x_end", x_end), ("score", score)):
+        if t is not None and tuple(t.shape) != (B, N, D):
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {(B, N, D)}")
+    dev = x_start.device
+    words_start, words_end = _sigma_words("sigma_start", sigma_start, B, dev), _sigma_words("sigma_end", sigma_end, B, dev)
+    if words_start.numel() != words_end.numel():
+        raise ValueError("sigma_start and sigma_end must both hold one value, or both one per structure")
+    stride = int(words_start.numel() == B and B > 1)
+    with_score = score is not None
+    values = score.detach().contiguous() if with_score else None
+    target = torch.empty(B, N, D, dtype=F32, device=dev)
+    gradient = torch.empty(B, N, D, dtype=F32, device=dev) if with_score else None
+    per_structure = torch.empty(B, dtype=F32, device=dev) if with_score else None
+    sums = torch.empty(B, dtype=torch.float64, device=dev) if with_score else None
+    loss = torch.empty(1, dtype=F32, device=dev) if with_score else None
+    call("mdx_consistency_loss", x_start.detach().contiguous(), x_end.detach().contiguous(), values, words_start, words_end, stride,
+         B, int(N), int(D), int(kmax), target, gradient, per_structure, sums, loss, status)
+    if with_score:
+        loss = _ConsistencyLossFunction.apply(score, loss[0], gradient) if score.requires_grad else loss[0]
+    return ConsistencyLoss(target=target, gradient=gradient, per_structure=per_structure, loss=loss)
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # fused MLP score network
 # ----------------------------------------------------------------------------------------------------------------

@@ -628,6 +628,30 @@ MDX_API int mdx_denoising_loss(const float* x0, const float* xt, const float* ta
                                float* per_structure, float* q_atm1, float* p_atm1, float* vb_term, float* ce_term,
                                uint32_t* status, mdx_stream_t stream);
 
+/* The consistency regularizer's target and loss (regularizers/consistency_regularizer.py:190-308, after Daras et al.;
+ * csrc/mdx_loss.hip): for a batch of structures x_start f32 [batch, N, D] at noise sigma_start that the sampler carried to
+ * x_end f32 [batch, N, D] at noise sigma_end < sigma_start, and the network's sigma-normalised score s f32 [batch, N, D] at the
+ * start,
+ *   u = wrap(x_start - x_end), sigma_eff = sqrt(sigma_start^2 - sigma_end^2),
+ *   target = (sigma_start / sigma_eff) x [sigma_eff x score of the wrapped Gaussian of width sigma_eff at u]
+ *            (mdx_wrapped_gaussian_sigma_normalized_score's formulas and truncation kmax in [0, 64]),
+ *   per_structure[b] = sum over the structure of s (s - 2 target), gradient = 2 (s - target) / batch = d loss / d s,
+ *   loss = (sum_b per_structure[b]) / batch, summed in structure order.
+ * sigma_start, sigma_end are DEVICE words (nothing is read on the host: the call can be captured): one f32 for the batch
+ * (sigma_stride 0) or f32 [batch] (sigma_stride 1); sigma_end = 0 is valid.  One workgroup per structure, then -- when loss is
+ * asked for -- one tiny launch for the batch total; N <= MDX_LOSS_MAX_ATOMS, D <= 3 and kmax <= 64, else MDX_ERR_UNSUPPORTED
+ * (before anything is launched).  Binary64 from the binary32 inputs promoted once, every output value rounded once; no atomics
+ * in the arithmetic, every sum in a fixed order: the same bits on every launch and hipGraph replay.  A structure whose
+ * sigma_start is not finite and positive, or not above a finite sigma_end >= 0, holds NaNs (MDX_STATUS_ANALYTICAL_SIGMA); an
+ * element with a coordinate that is not finite is NaN, and so is its structure's sum (MDX_STATUS_ANALYTICAL_COORDINATES).
+ * Outputs, each nullable: target, gradient f32 [batch, N, D]; per_structure f32 [batch]; loss f32 [1]; structure_sums
+ * f64 [batch], the unrounded sums that the second launch adds up: the caller's scratch, needed with loss.  With score == NULL
+ * only target is written (the other outputs must be NULL). */
+MDX_API int mdx_consistency_loss(const float* x_start, const float* x_end, const float* score, const float* sigma_start,
+                                 const float* sigma_end, int sigma_stride, int64_t batch, int number_of_atoms,
+                                 int spatial_dimension, int kmax, float* target, float* gradient, float* per_structure,
+                                 double* structure_sums, float* loss, uint32_t* status, mdx_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Fused score network: the reference's MLPScoreNetwork (models/score_networks/mlp_score_network.py:54-370,
  * unconditional forward, no permutation symmetrisation, no time prefactor) evaluated inside the kernels.
