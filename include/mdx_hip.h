@@ -943,7 +943,8 @@ MDX_API int mdx_egnn_table_gather(const float* table, const float* table_scalar,
  *                          coordinates x [n_nodes,3] with the Bloch wave vectors K [n_k,3] -- and h [n_nodes,H] =
  *                          EGNN.embedding_in([sigma | one_hot(atom type)]) = b + sigma W[:,0] + W[:,1 + a]
  *                          (emb_weight [H, n_features] row-major, n_features = 2 + number of atom types; sigma [B] per
- *                          structure, atoms_per_structure nodes each; the same binary32 operations as the reference's);
+ *                          structure, atoms_per_structure nodes each; the same binary32 operations as the reference's).
+ *                          An atom type outside [0, n_features - 2] contributes no column: h = b + sigma W[:,0];
  *                          second_out (nullable, [n_nodes, second_width]): a second linear map of the same input,
  *                          b2 + sigma W2[:,0] + W2[:,1 + a] -- with W2 = P W, b2 = P b (formed by the caller) the first
  *                          graph layer's per-node projections P h without an [n_nodes,H] x [H,2H] product;
