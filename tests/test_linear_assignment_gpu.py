@@ -10,7 +10,7 @@ from scipy.optimize import linear_sum_assignment
 
 pytestmark = pytest.mark.gpu
 
-SIZES = [1, 2, 3, 5, 63, 64, 65, 130, 256]
+SIZES = [1, 2, 3, 5, 63, 64, 65, 130, 256, 127, 128, 129, 192, 193, 255]      # appended to: a size's seed is its index
 PER_SIZE = 3
 
 
