@@ -2163,6 +2163,8 @@ __global__ __launch_bounds__(kBlock) void math_probe_kernel(int fn, const float*
         float r;
         if (fn == 0) r = logf_(v);
         else if (fn == 1) r = expf_(v);
+        else if (fn == 4) r = __builtin_amdgcn_cosf(v);         // the folded forwards' v_cos_f32 / v_sin_f32: v in revolutions
+        else if (fn == 5) r = __builtin_amdgcn_sinf(v);
         else {
             float s, c;
             sincospif_(v, s, c);
@@ -2872,7 +2874,7 @@ int mdx_rng_fill(int kind, uint64_t seed, uint32_t call, uint32_t draw, uint32_t
 
 int mdx_math_probe(int fn, const float* x, int64_t count, float* y, mdx_stream_t stream)
 {
-    if (fn < 0 || fn > 3 || count < 0 || (count > 0 && (!x || !y))) return MDX_ERR_INVALID_ARG;
+    if (fn < 0 || fn > 5 || count < 0 || (count > 0 && (!x || !y))) return MDX_ERR_INVALID_ARG;
     if (count == 0) return MDX_OK;
     hipLaunchKernelGGL(math_probe_kernel, dim3(flat_grid(count)), dim3(kBlock), 0, as_stream(stream), fn, x, count, y);
     return launch_status();

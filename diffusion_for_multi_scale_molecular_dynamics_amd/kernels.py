@@ -1645,6 +1645,9 @@ def rng_fill(kind: int, seed: int, call: int, draw: int, tag: int, n_items: int,
 
 
 def math_probe(fn: int, x: torch.Tensor) -> torch.Tensor:
+    """y = f(x) elementwise on the device (mdx_math_probe, tests only).  fn 0 logf, 1 expf, 2 sinpi, 3 cospi: the software
+    sequences of the arithmetic contract; fn 4 cos(2 pi x), 5 sin(2 pi x): the hardware v_cos_f32 / v_sin_f32 (x in
+    revolutions) that the folded forwards of mlp_pc_sample evaluate."""
     y = torch.empty_like(x)
     call("mdx_math_probe", fn, x, x.numel(), y)
     return y

@@ -123,7 +123,11 @@ typedef struct mdx_schedule {
 
 /* Counter-based RNG request: used only where the corresponding pre-drawn noise pointer is NULL.
  * value(item, k) comes from Philox4x32-10 with key = seed and
- * counter = (item, (call << 8) | k/4, draw, tag); draw = index * draw_stride + draw_offset. */
+ * counter = (item, (call << 8) | k/4, draw, tag); draw = index * draw_stride + draw_offset.
+ * item and k: per-atom draws (MDX_TAG_COORD, _GUMBEL, _BINARY) take item = b N + atom and k = the dimension / class; the lattice
+ * draw (MDX_TAG_LATTICE) takes item = the structure b and k = the lattice parameter, i.e. z_lattice [B, nl] is what
+ * mdx_rng_fill(kind 1, seed, call, draw, MDX_TAG_LATTICE, B, nl) writes.  index is the step's time index: a predictor from
+ * index i draws with draw = i * draw_stride, its corrector m with (i - 1) * draw_stride + 1 + m. */
 typedef struct mdx_rng {
     uint64_t seed;
     uint32_t call;          /* index of the sample() call (sub-batch) */
@@ -703,7 +707,11 @@ MDX_API int64_t mdx_mlp_image_floats(const mdx_mlp_t* mlp_host);
 MDX_API int mdx_mlp_pack_image(const mdx_mlp_t* mlp_host, float* image_out, mdx_stream_t stream);
 
 /* ScoreNetwork.forward of the MLP (mlp_score_network.py:281-370 + score_network.py:183-185: MASK logit = -inf):
- * one wavefront per structure, weights streamed from L2, activations in LDS.  time, sigma: [B,1]. */
+ * one wavefront per structure, activations in LDS.  time, sigma: [B,1].  The weights are staged into LDS -- one copy of the
+ * packed image, or the same re-layout done in the kernel when packed_image is NULL (the same bits) -- when the image of
+ * mdx_mlp_image_floats floats and the four wavefronts' regions fit 128 KiB of LDS together; a larger network is read from the
+ * caller's tensors in global memory (the same function; a row's sum is rounded differently in its last, partial quad).
+ * mdx_mlp_pc_sample applies the same limit. */
 MDX_API int mdx_mlp_forward(const mdx_mlp_t* mlp_host, const int64_t* atom_types, const float* x, const float* l,
                             const float* time, const float* sigma, int64_t batch, float* logits_out,
                             float* score_x_out, float* score_l_out, mdx_stream_t stream);
@@ -1000,7 +1008,9 @@ MDX_API int mdx_egnn_coord_aggregate(const float* edge_scalar, const float* coor
 MDX_API int mdx_rng_fill(int kind, uint64_t seed, uint32_t call, uint32_t draw, uint32_t tag, int64_t n_items, int width,
                  float* out, mdx_stream_t stream);
 
-/* MDX arithmetic probes (tests only): y = f(x) elementwise; fn 0 logf, 1 expf, 2 sinpi, 3 cospi. */
+/* MDX arithmetic probes (tests only): y = f(x) elementwise; fn 0 logf, 1 expf, 2 sinpi, 3 cospi (the software sequences of the
+ * arithmetic contract); 4 cos(2 pi x), 5 sin(2 pi x) as the hardware instructions v_cos_f32 / v_sin_f32 give them, x in
+ * revolutions -- what the folded forwards of mdx_mlp_pc_sample evaluate (not part of the bit-exact contract). */
 MDX_API int mdx_math_probe(int fn, const float* x, int64_t count, float* y, mdx_stream_t stream);
 
 #ifdef __cplusplus
