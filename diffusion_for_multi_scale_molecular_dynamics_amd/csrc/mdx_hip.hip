@@ -2229,6 +2229,7 @@ const char* mdx_status_string(int status)
         // the two bits a caller of the analytical score functions reads back from its status word
         case MDX_STATUS_ANALYTICAL_SIGMA: return "All values of sigma should be larger than zero.";
         case MDX_STATUS_ANALYTICAL_COORDINATES: return "the relative coordinates should all be in [0, 1)";
+        case MDX_STATUS_KS_NAN: return "a sample of the Kolmogorov-Smirnov metric holds a NaN";
         default: return "unknown status";
     }
 }

@@ -886,6 +886,104 @@ def consistency_loss(x_start, x_end, score=None, *, sigma_start, sigma_end, kmax
 
 
 # ----------------------------------------------------------------------------------------------------------------
+# sampling metrics: sort and two-sample Kolmogorov-Smirnov rank (csrc/mdx_metrics.hip)
+# ----------------------------------------------------------------------------------------------------------------
+KS_MAX_SAMPLES = _hip.KS_MAX_SAMPLES     # per sample: every product of a count and a reduced size stays below 2^48
+KS_SORT_TILE = _hip.KS_SORT_TILE         # keys per workgroup of the radix sort: the granule at which it changes behaviour
+
+
+def _ks_sample(name: str, values) -> torch.Tensor:
+    """A sample as the kernels take it: a flat contiguous device tensor; refused before any launch otherwise."""
+    if not isinstance(values, torch.Tensor):
+        raise ValueError(f"{name} must be a torch.Tensor, got {type(values).__name__}")
+    if values.numel() < 1:
+        raise ValueError(f"{name} is empty: the Kolmogorov-Smirnov distance of an empty sample is not defined")
+    if values.numel() > KS_MAX_SAMPLES:
+        raise ValueError(f"{name} holds {values.numel()} values, more than KS_MAX_SAMPLES = {KS_MAX_SAMPLES}")
+    if not values.is_cuda:
+        raise ValueError(f"{name} lives on {values.device}: the Kolmogorov-Smirnov kernels run on the GPU only (no CPU fallback)")
+    values = values.detach().reshape(-1)
+    if values.dtype not in (F32, F64):
+        values = values.to(F64)
+    return values.contiguous()
+
+
+def sort_keys(values, status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The ascending sort, f64 [n], of the n values of a device tensor (mdx_sort_keys): binary32 and binary64 are sorted in their
+    own width and widened exactly, any other dtype is taken as binary64; -0.0 comes out as +0.0; `values` is not modified.  A
+    hand-written radix sort: no vendor sort, no host read, capturable, the same bits on every replay.  A NaN sets
+    STATUS_KS_NAN in `status` (int32 [1], optional) and leaves the output unspecified."""
+    values = _ks_sample("values", values)
+    if status is not None and not status.is_cuda:
+        raise ValueError(f"status lives on {status.device}: the Kolmogorov-Smirnov kernels run on the GPU only")
+    n, wide = values.numel(), int(values.dtype == F64)
+    workspace = torch.empty(int(lib().mdx_sort_keys_workspace_bytes(n, wide)), dtype=torch.uint8, device=values.device)
+    out = torch.empty(n, dtype=F64, device=values.device)
+    call("mdx_sort_keys", values, n, wide, out, workspace, status)
+    return out
+
+
+def ks_two_sample_numerator(a, b, status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int64 [1] on the device: h = max over x of |c_a(x) n2/g - c_b(x) n1/g| with g = gcd(n1, n2) and c_s(x) the number of
+    elements of sample s that are <= x (mdx_sort_keys on both samples, then mdx_ks_two_sample_sorted); the two-sided
+    Kolmogorov-Smirnov distance is h / lcm(n1, n2).  Samples of different dtype are both taken as binary64.  No host read:
+    the call can be captured; a NaN in either sample sets STATUS_KS_NAN in `status` (int32 [1], optional)."""
+    a, b = _ks_sample("a", a), _ks_sample("b", b)
+    if a.device != b.device:
+        raise ValueError(f"a lives on {a.device} and b on {b.device}")
+    if a.dtype != b.dtype:
+        a, b = a.to(F64), b.to(F64)
+    a_sorted, b_sorted = sort_keys(a, status), sort_keys(b, status)
+    n1, n2 = a_sorted.numel(), b_sorted.numel()
+    workspace = torch.empty(int(lib().mdx_ks_two_sample_workspace_bytes(n1, n2)), dtype=torch.uint8, device=a.device)
+    numerator = torch.empty(1, dtype=I64, device=a.device)
+    call("mdx_ks_two_sample_sorted", a_sorted, n1, b_sorted, n2, workspace, numerator)
+    return numerator
+
+
+def kolmogorov_limit_p_value(scaled_distance: float) -> float:
+    """Kolmogorov's limiting law Q(lambda) = P(sup |B| > lambda) in binary64 host arithmetic, clipped to [0, 1]:
+    2 sum_{k>=1} (-1)^(k-1) exp(-2 k^2 lambda^2) for lambda >= 1.18, 1 - sqrt(2 pi) / lambda sum_{k>=1} exp(-(2k-1)^2 pi^2 /
+    (8 lambda^2)) below that, 1 for lambda <= 0 (scipy.stats.kstwobign.sf).  Either series needs a handful of terms there."""
+    import math
+    lam = float(scaled_distance)
+    if math.isnan(lam):
+        return lam
+    if lam <= 0.0:
+        return 1.0
+    total = 0.0
+    if lam >= 1.18:
+        for k in range(1, 8):
+            total += (-1.0) ** (k - 1) * math.exp(-2.0 * k * k * lam * lam)
+        value = 2.0 * total
+    else:
+        for k in range(1, 8):
+            total += math.exp(-((2 * k - 1) ** 2) * math.pi ** 2 / (8.0 * lam * lam))
+        value = 1.0 - math.sqrt(2.0 * math.pi) / lam * total
+    return min(1.0, max(0.0, value))
+
+
+def ks_two_sample(a, b):
+    """(distance, p_value), two Python floats, of the two-sided two-sample Kolmogorov-Smirnov test between the device tensors
+    a and b: what the reference asks scipy.stats.ks_2samp for (metrics/kolmogorov_smirnov_metrics.py:59-75), computed where
+    the samples are.  The distance is scipy's statistic, h / lcm(n1, n2) in one correctly rounded division of the integer
+    numerator (ks_two_sample_numerator); the numerator and the status word are read here, the feature's one point of host
+    contact.  A NaN in either sample gives (nan, nan), scipy's nan_policy='propagate'.
+    DEVIATION from the reference: the p-value is Kolmogorov's limiting law at lambda = d sqrt(n1 n2 / (n1 + n2))
+    (kolmogorov_limit_p_value), not scipy's method='auto' (exact path counting up to 10 000 samples, the finite-n kstwo law
+    above): the two differ by a few per cent at p ~ 0.3 (profiles/r16_ks_metrics.md)."""
+    import math
+    a, b = _ks_sample("a", a), _ks_sample("b", b)            # the refusals, before anything is allocated on a device
+    n1, n2 = a.numel(), b.numel()
+    status = torch.zeros(1, dtype=I32, device=a.device)
+    numerator = ks_two_sample_numerator(a, b, status)
+    if _take_status_bits(status, _hip.STATUS_KS_NAN) & _hip.STATUS_KS_NAN:
+        return float("nan"), float("nan")
+    distance = int(numerator.item()) / math.lcm(n1, n2)
+    return distance, kolmogorov_limit_p_value(distance * math.sqrt(n1 * n2 / (n1 + n2)))
+
+
+# ----------------------------------------------------------------------------------------------------------------
 # fused MLP score network
 # ----------------------------------------------------------------------------------------------------------------
 class MlpPack:

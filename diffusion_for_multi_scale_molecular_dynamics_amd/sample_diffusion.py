@@ -14,7 +14,12 @@ Differences, all additive:
   * `oracle: {name: stillinger_weber, sw_coeff_filename: <a LAMMPS .sw file, absolute or relative to the configuration>}` writes
     `energies.pt` (the Stillinger-Weber energy of every sample, CPU float64, as the reference's :243-251) from a HIP kernel;
     `name: lammps` is reported as out of scope (no LAMMPS here: samples.pt is written, energies.pt is not), Orion reporting
-    is absent.
+    is absent;
+  * `--reference_samples PATH` (a torch pickle of reference structures in the sample contract, with `potential_energy` when the
+    data set has it) together with a `metrics:` block that asks for something writes `metrics.pt`: the reference's validation
+    metrics of the samples against those structures (metrics.compute_sampling_metrics: Kolmogorov-Smirnov distances of
+    interatomic distances, energies and lattice parameters, from HIP kernels).  Without the flag the block is ignored, as in
+    the reference.
 """
 import argparse
 import logging
@@ -122,6 +127,9 @@ def main(args: Optional[Any] = None, axl_network: Optional[ScoreNetwork] = None)
                              "tools read them with a plain torch.load (default: this package's class)")
     parser.add_argument("--random_init_seed", type=int, default=None,
                         help="build the network of `model.score_network` with random weights (synthetic runs)")
+    parser.add_argument("--reference_samples", default=None,
+                        help="torch pickle of reference structures (the sample contract; `potential_energy` optional): with a "
+                             "`metrics:` block in the configuration, metrics.pt is written beside samples.pt")
     args = parser.parse_args(args)
 
     rank, world, device = _init_distributed(torch.device(args.device))
@@ -144,6 +152,7 @@ def main(args: Optional[Any] = None, axl_network: Optional[ScoreNetwork] = None)
                     "eager launches: reproduces the reference's run for a given torch.manual_seed).  `rng_mode: device` and "
                     "`use_hip_graph: true` in the `sampling:` block select the throughput modes (INTEGRATION.md).")
     oracle_parameters = oracle_parameters_of(hyper_params, args.config)
+    metrics_parameters = metrics_parameters_of(hyper_params, args.reference_samples, oracle_parameters)
     if axl_network is None:
         if args.random_init_seed is not None:
             torch.manual_seed(args.random_init_seed)
@@ -178,7 +187,23 @@ def main(args: Optional[Any] = None, axl_network: Optional[ScoreNetwork] = None)
                                       axl_network=axl_network, trajectory_initializer=trajectory_initializer,
                                       sampling_constraints=sampling_constraints)
     create_samples_and_write_to_disk(generator, sampling_parameters, oracle_parameters, device, args.output, rank,
-                                     for_reference=args.reference_pickles)
+                                     for_reference=args.reference_pickles, metrics_parameters=metrics_parameters,
+                                     reference_samples=args.reference_samples)
+
+
+def metrics_parameters_of(hyper_params: Dict[AnyStr, Any], reference_samples, oracle_parameters):
+    """The `metrics:` block as SamplingMetricsParameters when `--reference_samples` is given and the block asks for anything;
+    None otherwise (the block is then ignored, as in the reference's sample_diffusion).  Refused HERE, before sampling: a file
+    that does not exist, and `compute_energies` without a Stillinger-Weber `oracle:` block."""
+    if reference_samples is None or "metrics" not in hyper_params:
+        return None
+    from .metrics import as_sampling_metrics_parameters, asks_for_anything, check_energy_oracle
+    parameters = as_sampling_metrics_parameters(hyper_params["metrics"])
+    if not asks_for_anything(parameters):
+        return None
+    assert os.path.isfile(reference_samples), f"The reference samples '{reference_samples}' do not exist."
+    check_energy_oracle(parameters, oracle_parameters)
+    return parameters
 
 
 def oracle_parameters_of(hyper_params: Dict[AnyStr, Any], config_path) -> Optional[StillingerWeberParameters]:
@@ -203,10 +228,11 @@ def oracle_parameters_of(hyper_params: Dict[AnyStr, Any], config_path) -> Option
 
 
 def create_samples_and_write_to_disk(generator, sampling_parameters, oracle_parameters, device, output_path, rank: int = 0,
-                                     for_reference: bool = False):
+                                     for_reference: bool = False, metrics_parameters=None, reference_samples=None):
     """:208-270.  oracle_parameters: the reference's third argument, the energy oracle to evaluate the samples with: None or
     StillingerWeberParameters (rank 0 then writes energies.pt); LAMMPS and anything else is outside this package's scope and
-    refused; Orion reporting likewise absent."""
+    refused; Orion reporting likewise absent.  metrics_parameters (SamplingMetricsParameters) and reference_samples (the path
+    of a pickled reference batch), both or neither: rank 0 then writes metrics.pt."""
     if oracle_parameters is not None and not isinstance(oracle_parameters, StillingerWeberParameters):
         raise NotImplementedError("energy oracles other than StillingerWeberParameters (LAMMPS) are outside this package's scope: "
                                   "pass oracle_parameters=None")
@@ -241,6 +267,16 @@ def create_samples_and_write_to_disk(generator, sampling_parameters, oracle_para
         logger.info("Writing energies to disk...")
         with open(output_directory / "energies.pt", "wb") as fd:
             torch.save(torch.cat(chunks), fd)
+    if metrics_parameters is not None and reference_samples is not None:
+        from .metrics import compute_sampling_metrics
+        from .utils import reference_pickles
+        logger.info("Compute sampling metrics...")
+        metrics = compute_sampling_metrics(samples_batch, reference_pickles.load(reference_samples), metrics_parameters,
+                                           oracle_parameters, sampling_parameters.sample_batchsize)
+        for name, value in metrics.items():
+            logger.info("  %s : %.6g", name, value)
+        with open(output_directory / "metrics.pt", "wb") as fd:
+            torch.save(metrics, fd)
     logger.info("Done!")
 
 

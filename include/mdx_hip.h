@@ -76,6 +76,8 @@ extern "C" {
                                             atom-type results are NaN                                                       */
 #define MDX_STATUS_LOSS_INDEX 131072u    /* the same function: a time index outside [0, T) or an atom type outside [0, C); the
                                             structure's (atom's) atom-type results are NaN and no table entry is read       */
+#define MDX_STATUS_KS_NAN 262144u        /* mdx_sort_keys: a NaN among the values (scipy's nan_policy='propagate': the
+                                            Kolmogorov-Smirnov distance of such a sample is NaN); the output is unspecified  */
 
 #define MDX_MAX_CLASSES 8      /* C supported by the fused atom-type kernels */
 #define MDX_PREDICTOR 0
@@ -655,6 +657,38 @@ MDX_API int mdx_consistency_loss(const float* x_start, const float* x_end, const
                                  const float* sigma_end, int sigma_stride, int64_t batch, int number_of_atoms,
                                  int spatial_dimension, int kmax, float* target, float* gradient, float* per_structure,
                                  double* structure_sums, float* loss, uint32_t* status, mdx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Sampling metrics (csrc/mdx_metrics.hip): the two-sample Kolmogorov-Smirnov distance the reference takes between the samples'
+ * and the dataset's interatomic distances, energies and lattice parameters (metrics/kolmogorov_smirnov_metrics.py:42-75 --
+ * scipy.stats.ks_2samp on host copies), on the device the samples are on: a sort, then a rank kernel.
+ *
+ * mdx_sort_keys: sorted_out f64 [n] = the ascending sort of values, n binary32 (values_are_f64 0) or binary64 (1) numbers,
+ * widened exactly; values is not modified.  +-inf are ordinary keys; -0.0 and +0.0 are one key and come out as +0.0; a NaN
+ * anywhere sets MDX_STATUS_KS_NAN in status (nullable) and leaves the output unspecified.  A hand-written least-significant-
+ * digit radix sort on 8-bit digits of an orderable image of each value in the input's own width (4 passes for binary32, 8 for
+ * binary64; histogram, scan and stable scatter per pass over tiles of MDX_KS_SORT_TILE keys): no vendor sort, no allocation, no
+ * host read, stream-ordered and capturable; a stable keys-only sort has one correct output, so every launch and hipGraph
+ * replay gives the same bits.  workspace: mdx_sort_keys_workspace_bytes(n, values_are_f64) bytes, 16-byte aligned (0 for an n
+ * that is not supported).  1 <= n <= MDX_KS_MAX_SAMPLES, else MDX_ERR_UNSUPPORTED before anything is launched.
+ *
+ * mdx_ks_two_sample_sorted: for ascending a_sorted f64 [n1] and b_sorted f64 [n2] (no NaN), g = gcd(n1, n2) and c_s(x) = the
+ * number of elements of sample s that are <= x, numerator_out int64 [1] =
+ *   h = max over x in a U b of | c_a(x) (n2 / g) - c_b(x) (n1 / g) |,
+ * so that the Kolmogorov-Smirnov distance is d = h / lcm(n1, n2), ONE correctly rounded division left to the caller: scipy's
+ * two-sided statistic (searchsorted(..., side='right') on the concatenation, both signs), and the integer its exact branch
+ * rounds to.  Every product stays below 2^48 (MDX_KS_MAX_SAMPLES = 2^24).  One thread per element, two binary searches for the
+ * upper bound; integer block maxima and one small final workgroup: independent of the reduction order, no float atomics.
+ * workspace: mdx_ks_two_sample_workspace_bytes(n1, n2) bytes, 8-byte aligned.  1 <= n1, n2 <= MDX_KS_MAX_SAMPLES, else
+ * MDX_ERR_UNSUPPORTED before anything is launched. */
+#define MDX_KS_MAX_SAMPLES 16777216
+#define MDX_KS_SORT_TILE 2048
+MDX_API int64_t mdx_sort_keys_workspace_bytes(int64_t n, int values_are_f64);
+MDX_API int mdx_sort_keys(const void* values, int64_t n, int values_are_f64, double* sorted_out, void* workspace,
+                          uint32_t* status, mdx_stream_t stream);
+MDX_API int64_t mdx_ks_two_sample_workspace_bytes(int64_t n1, int64_t n2);
+MDX_API int mdx_ks_two_sample_sorted(const double* a_sorted, int64_t n1, const double* b_sorted, int64_t n2, void* workspace,
+                                     int64_t* numerator_out, mdx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Fused score network: the reference's MLPScoreNetwork (models/score_networks/mlp_score_network.py:54-370,
