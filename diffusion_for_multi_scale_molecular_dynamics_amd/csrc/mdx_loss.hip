@@ -16,11 +16,13 @@
 // arithmetic, every sum in a fixed order: a launch or a hipGraph replay always gives the same bits.  The status word alone is
 // OR-ed atomically, as everywhere in this library.  64-wide wavefronts are assumed (gfx950).
 //
-// The consistency regularizer's target and loss (mdx_consistency_loss) are the second member of the family, further down.
+// The consistency regularizer's target and loss (mdx_consistency_loss) are the second member of the family, further down; the
+// regression regularizer's target and error (mdx_regression_loss) the third.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/mdx_hip.h"
+#include "mdx_analytical_structure.hpp"
 #include "mdx_launch.hpp"
 #include "mdx_reduce.hpp"
 #include "mdx_wrapped_score.hpp"
@@ -295,8 +297,8 @@ __global__ __launch_bounds__(kBlock) void denoising_loss_kernel(const LossArgs a
 //       u = wrap(x_start - x_end), sigma_eff = sqrt(sigma_start^2 - sigma_end^2),
 //       target = (sigma_start / sigma_eff) x [sigma_eff x score of the wrapped Gaussian at u], term = s (s - 2 target),
 //       gradient = 2 (s - target) / batch; the structure's sum of terms as denoising_loss_kernel forms its means
-//   consistency_total_kernel    one workgroup: the binary64 sums of the structures, added in structure order by thread 0, divided
-//                               by the batch
+//   structure_total_kernel      one workgroup: the binary64 sums of the structures, added in structure order by thread 0, divided
+//                               by `divisor` (the batch here; the number of elements for the regression loss)
 struct ConsistencyArgs {
     const float *x_start, *x_end, *score, *sigma_start, *sigma_end;
     int sigma_stride, ND, kmax;
@@ -359,7 +361,8 @@ __global__ __launch_bounds__(kBlock) void consistency_loss_kernel(const Consiste
 
 // one workgroup of kBlock threads: the sums come through LDS kBlock at a time (one coalesced read, not one round trip to memory
 // per structure), thread 0 adds them in structure order
-__global__ __launch_bounds__(kBlock) void consistency_total_kernel(const double* structure_sums, int64_t batch, float* loss)
+__global__ __launch_bounds__(kBlock) void structure_total_kernel(const double* structure_sums, int64_t batch, double divisor,
+                                                                 float* loss)
 {
     __shared__ double chunk[kBlock];
     const int tid = threadIdx.x;
@@ -373,7 +376,67 @@ __global__ __launch_bounds__(kBlock) void consistency_total_kernel(const double*
         }
         __syncthreads();
     }
-    if (tid == 0) loss[0] = (float)(total / (double)batch);
+    if (tid == 0) loss[0] = (float)(total / divisor);
+}
+
+// ---- the regression regularizer's target and error (regularizers/regression_regularizer.py:35-68; see include/mdx_hip.h)
+//
+//   regression_loss_kernel      one workgroup per structure, kBlock threads.  The target t is the analytical score network's
+//       binary64 value (mdx_analytical_structure.hpp: the evaluation mdx_analytical_score rounds), or given_target promoted;
+//       e = s - t with t NOT rounded first, target = (float)t, gradient = 2 e / M, the structure's sum of e^2: per-thread sums
+//       in index order, then block_sum
+//   structure_total_kernel      the sums in structure order, divided by M = the number of elements of the batch
+struct RegressionArgs {
+    const float *x, *sigma, *score, *given_target, *sites;
+    double sigma_d_square, elements;
+    int kmax, use_permutations, N, D, permutations;
+    float *target, *gradient, *per_structure;
+    double* structure_sums;
+    uint32_t* status;
+};
+
+__global__ __launch_bounds__(kBlock) void regression_loss_kernel(const RegressionArgs a)
+{
+    __shared__ double partial[kMaxWaves];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    const int ND = a.N * a.D;
+    const float* score = a.score ? a.score + b * ND : nullptr;
+    float* target = a.target ? a.target + b * ND : nullptr;
+    float* gradient = a.gradient ? a.gradient + b * ND : nullptr;
+    const double elements = a.elements;
+    double sum = 0.0;
+    const auto element = [&](int64_t i, double t) {
+        store(target, i, t);
+        if (score) {
+            const double e = (double)score[i] - t;
+            store(gradient, i, 2.0 * e / elements);
+            sum += e * e;
+        }
+    };
+    if (a.given_target) {
+        const float* given = a.given_target + b * ND;
+        for (int64_t i = tid; i < ND; i += kBlock) element(i, (double)given[i]);
+    } else {
+        const int bad = analytical_structure(a.x + b * ND, a.sigma + b, 0, a.sites, a.sigma_d_square, a.kmax, a.use_permutations,
+                                             a.N, a.D, a.permutations, nullptr, element);
+        if (bad != 0) {
+            const double nan = __builtin_nan("");
+            for (int64_t i = tid; i < ND; i += kBlock) {
+                store(target, i, nan);
+                if (score) store(gradient, i, nan);
+            }
+            sum = nan;
+            if (tid == 0 && a.status) atomicOr(a.status, analytical_status_bits(bad));
+        }
+    }
+    if (score && (a.per_structure || a.structure_sums)) {
+        const double total = block_sum(sum, partial);
+        if (tid == 0) {
+            store(a.per_structure, b, total);
+            if (a.structure_sums) a.structure_sums[b] = total;
+        }
+    }
 }
 
 }  // namespace
@@ -465,7 +528,43 @@ int mdx_consistency_loss(const float* x_start, const float* x_end, const float* 
     threads = threads > kBlock ? kBlock : threads;
     hipLaunchKernelGGL(consistency_loss_kernel, dim3((unsigned)batch), dim3((unsigned)threads), 0, as_stream(stream), a);
     if (loss)
-        hipLaunchKernelGGL(consistency_total_kernel, dim3(1), dim3(kBlock), 0, as_stream(stream), structure_sums, batch, loss);
+        hipLaunchKernelGGL(structure_total_kernel, dim3(1), dim3(kBlock), 0, as_stream(stream), structure_sums, batch,
+                           (double)batch, loss);
+    return launch_status();
+}
+
+int mdx_regression_loss(const float* relative_coordinates, const float* sigmas, const float* score, const float* given_target,
+                        const float* equilibrium_relative_coordinates, double sigma_d_square, int kmax,
+                        int use_permutation_invariance, int64_t batch, int number_of_atoms, int spatial_dimension, float* target,
+                        float* gradient, float* per_structure, double* sums, float* loss, uint32_t* status, mdx_stream_t stream)
+{
+    const int N = number_of_atoms, D = spatial_dimension;
+    const bool analytical = given_target == nullptr;
+    if (batch < 0 || N < 1 || D < 1) return MDX_ERR_INVALID_ARG;
+    if (batch > 0x7fffffffLL) return MDX_ERR_UNSUPPORTED;
+    if (analytical) {
+        if (kmax < 0 || !(sigma_d_square > 0.0)) return MDX_ERR_INVALID_ARG;
+        if (N > kAnalyticalMaxAtoms || D > kAnalyticalMaxDimension || kmax > kAnalyticalMaxTranslation) return MDX_ERR_UNSUPPORTED;
+        if (use_permutation_invariance && N > kMaxPermutedAtoms) return MDX_ERR_UNSUPPORTED;
+        if (!relative_coordinates || !sigmas || !equilibrium_relative_coordinates) return MDX_ERR_INVALID_ARG;
+    } else {
+        if ((int64_t)N * D > 0x7fffffffLL) return MDX_ERR_UNSUPPORTED;
+        if (!score) return MDX_ERR_INVALID_ARG;
+    }
+    if (!score && (gradient || per_structure || sums || loss)) return MDX_ERR_INVALID_ARG;
+    if (!score && !target) return MDX_ERR_INVALID_ARG;
+    if (loss && !sums) return MDX_ERR_INVALID_ARG;
+    if (batch == 0) return MDX_OK;
+    RegressionArgs a;
+    a.x = relative_coordinates, a.sigma = sigmas, a.score = score, a.given_target = given_target;
+    a.sites = equilibrium_relative_coordinates;
+    a.sigma_d_square = sigma_d_square, a.elements = (double)batch * (double)N * (double)D;
+    a.kmax = kmax, a.use_permutations = (analytical && use_permutation_invariance) ? 1 : 0, a.N = N, a.D = D;
+    a.permutations = analytical ? analytical_permutations(N, use_permutation_invariance) : 1;
+    a.target = target, a.gradient = gradient, a.per_structure = per_structure, a.structure_sums = sums;
+    a.status = status;
+    hipLaunchKernelGGL(regression_loss_kernel, dim3((unsigned)batch), dim3(kBlock), 0, as_stream(stream), a);
+    if (loss) hipLaunchKernelGGL(structure_total_kernel, dim3(1), dim3(kBlock), 0, as_stream(stream), sums, batch, a.elements, loss);
     return launch_status();
 }
 

@@ -832,8 +832,8 @@ def _sigma_words(name: str, sigma, batch: int, device) -> torch.Tensor:
 
 
 class _ConsistencyLossFunction(torch.autograd.Function):
-    """loss(score) of mdx_consistency_loss for a score that requires grad: backward is grad_output x the kernel's own gradient
-    buffer, 2 (s - target) / B, no second launch."""
+    """loss(score) of mdx_consistency_loss or mdx_regression_loss for a score that requires grad: backward is grad_output x the
+    kernel's own gradient buffer (2 (s - target) / B; / (B N D) for the regression loss), no second launch."""
 
     @staticmethod
     def forward(ctx, score, loss, gradient):
@@ -883,6 +883,74 @@ def consistency_loss(x_start, x_end, score=None, *, sigma_start, sigma_end, kmax
     if with_score:
         loss = _ConsistencyLossFunction.apply(score, loss[0], gradient) if score.requires_grad else loss[0]
     return ConsistencyLoss(target=target, gradient=gradient, per_structure=per_structure, loss=loss)
+
+
+RegressionLoss = namedtuple("RegressionLoss", ["target", "gradient", "per_structure", "loss"])
+
+
+def regression_loss(score=None, *, target=None, relative_coordinates=None, sigmas=None, equilibrium_relative_coordinates=None,
+                    sigma_d_square: Optional[float] = None, kmax: Optional[int] = None, use_permutation_invariance: bool = False,
+                    status: Optional[torch.Tensor] = None) -> RegressionLoss:
+    """The regression regularizer's target and error (mdx_regression_loss), one call with no host read: score f32 [B, N, D]
+    against a target that is either GIVEN (`target` f32 [B, N, D]) or the analytical score network's at `relative_coordinates`
+    f32 [B, N, D] with `sigmas` (B values, one per structure), `equilibrium_relative_coordinates` f32 [N, D], `sigma_d_square`,
+    `kmax` and `use_permutation_invariance` -- kernels.analytical_score's evaluation, kept in binary64 for the subtraction.
+    Returns a RegressionLoss of f32 tensors: target [B, N, D] (the bits of kernels.analytical_score; the given tensor's values);
+    gradient [B, N, D] = 2 (score - target) / (B N D); per_structure [B], the sums of (score - target)^2; loss (0-dim), their sum
+    over B N D: mean((score - target)^2).  Without `score` (analytical target only) only target is made.  When `score` requires
+    grad, loss carries it: its backward returns grad_output x gradient.  An invalid sigma or coordinate gives NaNs in its
+    structure and in loss, and its bit in `status` (raise_analytical_status)."""
+    given = target is not None
+    _device_only("the regression loss", score=score, target=target, relative_coordinates=relative_coordinates,
+                 sigmas=sigmas if isinstance(sigmas, torch.Tensor) else None,
+                 equilibrium_relative_coordinates=equilibrium_relative_coordinates, status=status)
+    if given:
+        if score is None:
+            raise ValueError("a given target needs a score to be compared with")
+        if relative_coordinates is not None or sigmas is not None or equilibrium_relative_coordinates is not None:
+            raise ValueError("give either target, or relative_coordinates, sigmas and equilibrium_relative_coordinates: not both")
+        shaped = target
+    else:
+        missing = [name for name, value in (("relative_coordinates", relative_coordinates), ("sigmas", sigmas),
+                                            ("equilibrium_relative_coordinates", equilibrium_relative_coordinates),
+                                            ("sigma_d_square", sigma_d_square), ("kmax", kmax)) if value is None]
+        if missing:
+            raise ValueError(f"without a given target the analytical one needs {', '.join(missing)}")
+        shaped = relative_coordinates
+    if shaped.dim() != 3:
+        raise ValueError(f"{'target' if given else 'relative_coordinates'} has shape {tuple(shaped.shape)}, expected [B, N, D]")
+    B, N, D = shaped.shape
+    if B < 1:
+        raise ValueError("the regression loss of an empty batch is not defined")
+    if score is not None and tuple(score.shape) != (B, N, D):
+        raise ValueError(f"score has shape {tuple(score.shape)}, expected {(B, N, D)}")
+    dev = shaped.device
+    sites = None
+    if not given:
+        if tuple(equilibrium_relative_coordinates.shape) != (N, D):
+            raise ValueError(f"equilibrium_relative_coordinates has shape {tuple(equilibrium_relative_coordinates.shape)}, "
+                             f"expected {(N, D)}")
+        if not isinstance(sigmas, torch.Tensor):
+            sigmas = torch.full((B,), float(sigmas), dtype=F32, device=dev)
+        if sigmas.numel() != B:
+            raise ValueError(f"sigmas has shape {tuple(sigmas.shape)}: expected one value per structure, [{B}]")
+        sigmas = sigmas.detach().to(dtype=F32).reshape(-1).contiguous()
+        relative_coordinates = relative_coordinates.detach().to(dtype=F32).contiguous()
+        sites = equilibrium_relative_coordinates.detach().to(dtype=F32).contiguous()
+    with_score = score is not None
+    values = score.detach().to(dtype=F32).contiguous() if with_score else None
+    given_values = target.detach().to(dtype=F32).contiguous() if given else None
+    out_target = torch.empty(B, N, D, dtype=F32, device=dev)
+    gradient = torch.empty(B, N, D, dtype=F32, device=dev) if with_score else None
+    per_structure = torch.empty(B, dtype=F32, device=dev) if with_score else None
+    sums = torch.empty(B, dtype=torch.float64, device=dev) if with_score else None
+    loss = torch.empty(1, dtype=F32, device=dev) if with_score else None
+    call("mdx_regression_loss", relative_coordinates if not given else None, sigmas if not given else None, values, given_values,
+         sites, 0.0 if given else float(sigma_d_square), 0 if given else int(kmax), int(bool(use_permutation_invariance)),
+         B, int(N), int(D), out_target, gradient, per_structure, sums, loss, status)
+    if with_score:
+        loss = _ConsistencyLossFunction.apply(score, loss[0], gradient) if score.requires_grad else loss[0]
+    return RegressionLoss(target=out_target, gradient=gradient, per_structure=per_structure, loss=loss)
 
 
 # ----------------------------------------------------------------------------------------------------------------

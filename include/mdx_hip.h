@@ -658,6 +658,32 @@ MDX_API int mdx_consistency_loss(const float* x_start, const float* x_end, const
                                  int spatial_dimension, int kmax, float* target, float* gradient, float* per_structure,
                                  double* structure_sums, float* loss, uint32_t* status, mdx_stream_t stream);
 
+/* The regression regularizer's target and error (regularizers/regression_regularizer.py:35-68; csrc/mdx_loss.hip): how far a
+ * network's sigma-normalised score s f32 [batch, N, D] is from a known target t, with M = batch N D,
+ *   e = s - t (binary64, t NOT rounded first), target = t rounded once, gradient = 2 e / M = d loss / d s,
+ *   sums[b] = sum over the structure of e^2, per_structure[b] = sums[b] rounded once,
+ *   loss = (sum_b sums[b]) / M, summed in structure order: the reference's mean((s - t)^2).
+ * Two modes.  given_target == NULL: t is the analytical score network's score at relative_coordinates f32 [batch, N, D] with
+ * sigmas f32 [batch] (one per structure) and equilibrium_relative_coordinates f32 [N, D] -- exactly mdx_analytical_score's
+ * evaluation (the same code: the plain path, and the N! permutations with use_permutation_invariance), kept in binary64;
+ * target then holds the bits mdx_analytical_score gives.  Its limits hold: N <= 1024, D <= 3, kmax in [0, 64], N <= 8 with
+ * permutations, else MDX_ERR_UNSUPPORTED; sigma_d_square > 0.  A structure holding a sigma that is not finite and positive or a
+ * coordinate outside [0, 1) gets NaNs in target, gradient and per_structure, loss is NaN, and its MDX_STATUS_ANALYTICAL_SIGMA /
+ * _COORDINATES bit goes to status (nullable); the other structures are unaffected.  given_target != NULL: t is that tensor,
+ * f32 [batch, N, D], promoted; relative_coordinates, sigmas and the sites are not read (they may be NULL), sigma_d_square,
+ * kmax and use_permutation_invariance are ignored, score is required, and any N D that fits an int is served.
+ * One workgroup per structure, then -- when loss is asked for -- one tiny launch for the batch total; no host read.  Binary64
+ * from the binary32 inputs promoted once, every output value rounded once; no atomics in the arithmetic, every sum in a fixed
+ * order: the same bits on every launch and hipGraph replay.  Outputs, each nullable: target, gradient f32 [batch, N, D];
+ * per_structure f32 [batch]; loss f32 [1]; sums f64 [batch], the unrounded sums that the second launch adds up: the caller's
+ * scratch, needed with loss.  With score == NULL (analytical mode only) only target is written (the other outputs must be
+ * NULL). */
+MDX_API int mdx_regression_loss(const float* relative_coordinates, const float* sigmas, const float* score,
+                                const float* given_target, const float* equilibrium_relative_coordinates, double sigma_d_square,
+                                int kmax, int use_permutation_invariance, int64_t batch, int number_of_atoms,
+                                int spatial_dimension, float* target, float* gradient, float* per_structure, double* sums,
+                                float* loss, uint32_t* status, mdx_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Sampling metrics (csrc/mdx_metrics.hip): the two-sample Kolmogorov-Smirnov distance the reference takes between the samples'
  * and the dataset's interatomic distances, energies and lattice parameters (metrics/kolmogorov_smirnov_metrics.py:42-75 --
