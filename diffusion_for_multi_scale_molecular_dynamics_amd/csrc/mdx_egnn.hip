@@ -93,7 +93,7 @@ __global__ __launch_bounds__(kBlock) void egnn_node_inputs_kernel(const float* _
             h2[t] = v;
         }
     }
-    for (int64_t t = t0; t < n_nodes * H; t += stride) {
+    for (int64_t t = t0; h && t < n_nodes * H; t += stride) {      // (h nullable: a caller that keeps one row per class)
         const int64_t i = t / H;
         const int j = (int)(t - i * H);
         const float s = sigma[i / atoms_per_structure];
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(kBlock) void egnn_node_inputs_rows_kernel(const flo
     extern __shared__ float tables[];                   // [ (1 + F) H | (1 + F) H2 ]
     float* t1 = tables;
     float* t2 = tables + (1 + F) * H;
-    for (int j = threadIdx.x; j < H; j += blockDim.x) {
+    for (int j = threadIdx.x; h && j < H; j += blockDim.x) {
         t1[j] = b[j];
         for (int f = 0; f < F; ++f) t1[(1 + f) * H + j] = w[(int64_t)j * F + f];
     }
@@ -183,13 +183,15 @@ __global__ __launch_bounds__(kBlock) void egnn_node_inputs_rows_kernel(const flo
                 uplift(kr, z[2 * (i0 * n_k + k)], z[2 * (i0 * n_k + k) + 1]);
             }
         }
+        if (!h && !h2) continue;                        // (both nullable: z alone)
         for (int g = 0; g < per && i0 + g < n_nodes; ++g) {
             const int64_t i = i0 + g;
             const float s = sigma[i / atoms_per_structure];
             const int64_t a = atom_types[i];
             if (h2)
                 for (int q = lane; q < (H2 >> 2); q += 64) reinterpret_cast<float4*>(h2 + i * H2)[q] = embed_quad(t2, H2, q, s, a, F);
-            for (int q = lane; q < (H >> 2); q += 64) reinterpret_cast<float4*>(h + i * H)[q] = embed_quad(t1, H, q, s, a, F);
+            if (h)
+                for (int q = lane; q < (H >> 2); q += 64) reinterpret_cast<float4*>(h + i * H)[q] = embed_quad(t1, H, q, s, a, F);
         }
     }
 }
@@ -407,8 +409,9 @@ int mdx_egnn_node_inputs_keyed(const float* x, const float* k_vectors, int n_k, 
 {
     if (n_nodes < 0 || n_k < 1 || atoms_per_structure < 1 || n_features < 2 || H < 1) return MDX_ERR_INVALID_ARG;
     if (n_nodes == 0) return MDX_OK;
-    if (!x || !k_vectors || !sigma || !atom_types || !emb_weight || !emb_bias || !z_out || !h_out) return MDX_ERR_INVALID_ARG;
+    if (!x || !k_vectors || !sigma || !atom_types || !emb_weight || !emb_bias || !z_out) return MDX_ERR_INVALID_ARG;
     if (second_out && (!second_weight || !second_bias || second_width < 1)) return MDX_ERR_INVALID_ARG;
+    // (the rows kernel lays t2 out behind t1 whether or not h_out is given)
     const size_t table_bytes = sizeof(float) * (size_t)(1 + n_features) * ((size_t)H + (second_out ? (size_t)second_width : 0));
     if ((H & 3) == 0 && (!second_out || (second_width & 3) == 0) && table_bytes <= 48 * 1024) {
         // a workgroup stages the tables once (<= 48 KB from L2) and then only stores: eight wavefronts per SIMD keep enough 16-byte

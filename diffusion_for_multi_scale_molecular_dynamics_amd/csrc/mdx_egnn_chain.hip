@@ -99,6 +99,10 @@ struct ChainArgs {
     // would rebuild and the forward's sigma.  (Behind every other member: no other argument's offset moves.)
     const uint32_t* table_key;
     const float* table_sigma;
+    // MODE 3 through mdx_node_mlp_rows_indexed, else null: rows_in / residual hold ONE row per class ([n_classes][ld_in]) and
+    // row r reads row row_class[r] of them (an index outside [0, n_classes): row 0 and MDX_STATUS_EGNN_TABLE).  (Last again.)
+    const int64_t* row_class;
+    int n_classes;
 };
 
 constexpr float kLog2e = 1.44269504088896340736f, kLn2 = 0.69314718055994530942f;
@@ -901,6 +905,20 @@ __global__ __launch_bounds__(kWaves* kWave, 1) void egnn_edge_chain_kernel(Chain
             for (int es = 0; es < NS; ++es) count += __builtin_amdgcn_ballot_w64(is_live(es)) != 0 ? total / NS : 0;
             return __builtin_amdgcn_readfirstlane(count);
         };
+        // The row of rows_in / residual that this lane's row es reads: its own, or -- MODE 3 with ChainArgs::row_class -- the row
+        // of its class.  Evaluated where a row is read (twice per tile: the operand, the residual), not carried through the chain.
+        // report: a live row's class outside the table raises MDX_STATUS_EGNN_TABLE (once per tile: with the operand).
+        [[maybe_unused]] auto source_row = [&](int es, bool report) -> int64_t {
+            if constexpr (MODE == 3) {
+                if (p.row_class) {
+                    const int64_t c = p.row_class[e[es]];
+                    const bool inside = c >= 0 && c < (int64_t)p.n_classes;
+                    if (report && !inside && is_live(es) && p.status) atomicOr(p.status, MDX_STATUS_EGNN_TABLE);
+                    return inside ? c : 0;
+                }
+            }
+            return e[es];
+        };
         Act<H, PREC> xa, xb;
         // exact-f32 kernels with ChainArgs::act_max: the largest |u| this lane has written since the last flush_max(); a flush
         // reduces it over the wavefront and raises the position's word (float bits of non-negative values order like integers)
@@ -1029,10 +1047,15 @@ __global__ __launch_bounds__(kWaves* kWave, 1) void egnn_edge_chain_kernel(Chain
         } else {
             // the rows themselves (the caller's activations, carried as 2^b log2(e) x inside the chain)
             const float kIn = end_factor(1);
+            int64_t row[NS];
+            if constexpr (MODE == 3) {
+#pragma unroll
+                for (int es = 0; es < NS; ++es) row[es] = source_row(es, true);
+            }
 #pragma unroll
             for (int q8 = 0; q8 < H / 8; ++q8) {
                 const int es = L::es(q8 & 3), off = 32 * (q8 >> 2) + L::fb(q8 & 3, h);
-                const f32x4 a = *(const f32x4*)(p.rows_in + e[es] * p.ld_in + off);
+                const f32x4 a = *(const f32x4*)(p.rows_in + (MODE == 3 ? row[es] : e[es]) * p.ld_in + off);
                 if constexpr (SPLIT) {
                     put_pair<H>(xa, q8 >> 2, 4 * (q8 & 3), a[0] * kIn, a[1] * kIn);
                     put_pair<H>(xa, q8 >> 2, 4 * (q8 & 3) + 2, a[2] * kIn, a[3] * kIn);
@@ -1305,6 +1328,11 @@ __global__ __launch_bounds__(kWaves* kWave, 1) void egnn_edge_chain_kernel(Chain
             flush_max(layers);
             const bool project = MODE == 3 && p.proj_out != nullptr;       // out is also the operand of two more linear layers
             const float kOut = end_factor(2);
+            int64_t row[NS];
+            if constexpr (MODE == 3) {
+#pragma unroll
+                for (int es = 0; es < NS; ++es) row[es] = p.residual ? source_row(es, false) : e[es];
+            }
 #pragma unroll
             for (int q8 = 0; q8 < H / 8; ++q8) {
                 const int t = q8 >> 2, q = q8 & 3, es = L::es(q), off = 32 * t + L::fb(q, h);
@@ -1317,7 +1345,7 @@ __global__ __launch_bounds__(kWaves* kWave, 1) void egnn_edge_chain_kernel(Chain
                 }
                 if (is_live(es)) {
                     if (p.residual) {
-                        const f32x4 r4 = *(const f32x4*)(p.residual + e[es] * p.ld_in + off);
+                        const f32x4 r4 = *(const f32x4*)(p.residual + (MODE == 3 ? row[es] : e[es]) * p.ld_in + off);
 #pragma unroll
                         for (int i = 0; i < 4; ++i) v[i] = r4[i] + v[i];
                     }
@@ -1976,7 +2004,7 @@ int mdx_mlp_chain_rows(const mdx_egnn_chain_t* c, const float* x, const float* r
 // node_in: [n_rows][ld] rows whose first H columns are h; agg: [n_rows][ld_agg]
 static int node_mlp_rows(const mdx_egnn_chain_t* c, const float* node_in, int64_t ld, const float* agg, int64_t ld_agg,
                          int add_residual, int64_t n_rows, const int64_t* n_rows_dev, float* out, float* proj_out,
-                         uint32_t* status, mdx_stream_t stream);
+                         uint32_t* status, mdx_stream_t stream, const int64_t* row_class = nullptr, int n_classes = 0);
 
 int mdx_node_mlp_rows(const mdx_egnn_chain_t* c, const float* node_in, int add_residual, int64_t n_rows,
                       const int64_t* n_rows_dev, float* out, float* proj_out, uint32_t* status, mdx_stream_t stream)
@@ -1993,9 +2021,18 @@ int mdx_node_mlp_rows_split(const mdx_egnn_chain_t* c, const float* h, const flo
     return node_mlp_rows(c, h, c->hidden, agg, c->hidden, add_residual, n_rows, n_rows_dev, out, proj_out, status, stream);
 }
 
+int mdx_node_mlp_rows_indexed(const mdx_egnn_chain_t* c, const float* class_rows, int n_classes, const int64_t* row_class,
+                              const float* agg, int add_residual, int64_t n_rows, const int64_t* n_rows_dev, float* out,
+                              float* proj_out, uint32_t* status, mdx_stream_t stream)
+{
+    if (!c || n_classes < 1 || (n_rows > 0 && !row_class)) return MDX_ERR_INVALID_ARG;
+    return node_mlp_rows(c, class_rows, c->hidden, agg, c->hidden, add_residual, n_rows, n_rows_dev, out, proj_out, status, stream,
+                         row_class, n_classes);
+}
+
 static int node_mlp_rows(const mdx_egnn_chain_t* c, const float* node_in, int64_t ld, const float* agg, int64_t ld_agg,
                          int add_residual, int64_t n_rows, const int64_t* n_rows_dev, float* out, float* proj_out,
-                         uint32_t* status, mdx_stream_t stream)
+                         uint32_t* status, mdx_stream_t stream, const int64_t* row_class, int n_classes)
 {
     if (!c || n_rows < 0) return MDX_ERR_INVALID_ARG;
     if (c->n_message_layers < 3 || c->n_coord_layers != 0 || (c->precision < 0 || c->precision > 2)) return MDX_ERR_INVALID_ARG;
@@ -2010,6 +2047,7 @@ static int node_mlp_rows(const mdx_egnn_chain_t* c, const float* node_in, int64_
     a.rows_in = node_in; a.residual = add_residual ? node_in : nullptr; a.rows_out = out; a.status = status;
     a.ld_in = ld; a.rows_in2 = agg; a.ld_in2 = ld_agg;
     a.proj_out = proj_out;
+    a.row_class = row_class; a.n_classes = n_classes;
     if (proj_out && c->n_message_layers + 2 > MDX_EGNN_CHAIN_MAX_LAYERS) return MDX_ERR_UNSUPPORTED;
     const int layers = a.n_message;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);

@@ -368,7 +368,9 @@ __device__ __forceinline__ void posterior(const float* __restrict__ logits, int 
                                           float small_eps, float* p, const FixedSoftmaxC2& fixed = FixedSoftmaxC2{0.0f, 0.0f, 0})
 {
     float e[MDX_MAX_CLASSES], lg[MDX_MAX_CLASSES];
-    MDX_FOR_CLASSES(c) lg[c] = logits[c];
+    // (logits == nullptr: one atom type and a caller that did not compute them -- (0, -inf), see FixedSoftmaxC2; C == 2 is
+    // checked on the host)
+    MDX_FOR_CLASSES(c) lg[c] = logits ? logits[c] : (c == 0 ? 0.0f : -__builtin_huge_valf());
     if (C == 2 && fixed.valid && lg[1] == -__builtin_huge_valf() && __builtin_fabsf(lg[0]) < __builtin_huge_valf()) {
         MDX_FOR_CLASSES(c) e[c] = c == 0 ? fixed.e0 : fixed.e1;
     } else {
@@ -576,7 +578,7 @@ __device__ __forceinline__ void pc_update_structure(const PcArgs& p, const PcSte
             bool tabulated = false;
             float pr_mask = 0.0f, log_eps = 0.0f;
             if (C == 2 && v.p2_table && !v.p_out) {
-                const float l0 = v.logits[n * C], l1 = v.logits[n * C + 1];
+                const float l0 = v.logits ? v.logits[n * C] : 0.0f, l1 = v.logits ? v.logits[n * C + 1] : -__builtin_huge_valf();
                 if (l1 == -__builtin_huge_valf() && __builtin_fabsf(l0) < __builtin_huge_valf()) {
                     tabulated = true;
                     const int sel = a_t != 0;
@@ -586,7 +588,7 @@ __device__ __forceinline__ void pc_update_structure(const PcArgs& p, const PcSte
                 }
             }
             if (!tabulated) {
-                posterior(v.logits + n * C, a_t, st.q, st.qbar, st.qbar_tm1, C, p.small_eps, pr, st.fixed_c2);
+                posterior(v.logits ? v.logits + n * C : nullptr, a_t, st.q, st.qbar, st.qbar_tm1, C, p.small_eps, pr, st.fixed_c2);
                 MDX_FOR_CLASSES(c) if (c == M) pr_mask = pr[c];
             }
             if (v.gumbel) {
@@ -2403,7 +2405,10 @@ int mdx_pc_step_update(const mdx_schedule_t* sched_host, int mode, int index_i, 
                                   spatial_dimension, atom_types_out, status, a);
     if (rc != MDX_OK || batch == 0) return rc;
     if (!x || !score_x || !x_out || !l || !l_out) return MDX_ERR_INVALID_ARG;
-    if (f->update_atom_types && (!atom_types || !logits || !atom_types_out)) return MDX_ERR_INVALID_ARG;
+    if (f->update_atom_types && (!atom_types || !atom_types_out)) return MDX_ERR_INVALID_ARG;
+    // no logits: one atom type only, where they are (finite, -inf) whatever the network computes (see FixedSoftmaxC2), and
+    // never with the probabilities asked for
+    if (f->update_atom_types && !logits && (a.C != 2 || a.p_out)) return MDX_ERR_INVALID_ARG;
     if (!f->use_fixed_lattice_parameters && !score_l) return MDX_ERR_INVALID_ARG;
     if ((int64_t)batch * number_of_atoms > 0xffffffffLL) return MDX_ERR_UNSUPPORTED;   // 32-bit Philox item index
     a.update_types = f->update_atom_types;

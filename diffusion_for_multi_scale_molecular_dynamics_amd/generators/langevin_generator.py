@@ -329,6 +329,19 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
     # ---------------------------------------------------------------------------------------------------------
     # one step = network forward + ONE fused update kernel
     # ---------------------------------------------------------------------------------------------------------
+    def _logits_unread(self, update_types: bool, predictions_unread: bool) -> bool:
+        """Does nobody read predictions.A of a step?  The caller drops the returned predictions, nothing is recorded,
+        _get_model_predictions is LangevinGenerator's own (not a subclass's override, not a replacement set on the class or on
+        the instance: whoever puts one there sees every forward whole), no forward hook sits on the network or on a module
+        inside it -- and the update itself does not need them: it leaves the types alone, or there is ONE atom type, where
+        the MASK logit is forced to -inf and the update makes the same of every (finite, -inf) (mdx_pc_step_update, logits ==
+        NULL).  When in doubt the hint is not given."""
+        constant_logits = self.num_classes == 2
+        return bool(predictions_unread and (not update_types or constant_logits) and not self.record
+                    and not self.record_atom_type_update and "_get_model_predictions" not in self.__dict__
+                    and type(self)._get_model_predictions is _OWN_GET_MODEL_PREDICTIONS
+                    and not hooks.outputs_watched(self.axl_network))
+
     def _step(self, mode: int, composition: AXL, index_i: int, cartesian_forces: torch.Tensor, draw_offset: int,
               d_index: Optional[torch.Tensor] = None, in_place: bool = False, predictions_unread: bool = False):
         """predictions_unread: the caller drops the returned predictions (the device-resident loop)."""
@@ -339,13 +352,7 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
         time_t, sigma_t = self._time_sigma(batch, device)
         kernels.fill_time_sigma(sched, mode, index_i, d_index, time_t, sigma_t)
         update_types = mode == MDX_PREDICTOR or self.atom_type_transition_in_corrector
-        # Nobody reads predictions.A of this step: the update does not touch the types, the caller drops the predictions, nothing
-        # is recorded, _get_model_predictions is LangevinGenerator's own (not a subclass's override, not a replacement set on the
-        # class or on the instance: whoever puts one there sees every forward whole) and no forward hook sits on the network or
-        # on a module inside it.  When in doubt the hint is not given.
-        unread = (predictions_unread and not update_types and not self.record and not self.record_atom_type_update
-                  and "_get_model_predictions" not in self.__dict__
-                  and type(self)._get_model_predictions is _OWN_GET_MODEL_PREDICTIONS and not hooks.outputs_watched(self.axl_network))
+        unread = self._logits_unread(update_types, predictions_unread)
         with hooks.logits_unread(self.axl_network) if unread else contextlib.nullcontext():
             predictions = self._get_model_predictions(composition, time_t, sigma_t, cartesian_forces)
 
@@ -382,7 +389,9 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
             l_out = composition.L
         else:
             l_out = torch.empty_like(composition.L)
-        logits = predictions.A.contiguous() if update_types else None
+        logits = predictions.A.contiguous() if update_types and predictions.A is not None else None
+        if update_types and logits is None and not unread:
+            raise MdxError("the score network returned no atom-type logits for a step that reads them")
         kernels.pc_step_update(sched, mode, index_i, d_index, self._flags(update_types),
                                a_in if update_types else None, x, composition.L, logits,
                                predictions.X.contiguous(),
@@ -586,7 +595,7 @@ class LangevinGenerator(PredictorCorrectorAXLGenerator):
         device; in place."""
         visits = 1 + self.resampling_steps if visits is None else visits
         for self._visit in range(visits):
-            comp, _ = self._step(MDX_PREDICTOR, comp, 1, forces, 0, d_index=d_index, in_place=True)
+            comp, _ = self._step(MDX_PREDICTOR, comp, 1, forces, 0, d_index=d_index, in_place=True, predictions_unread=True)
             comp = self._after_predictor(comp, 0, d_index=d_index)
             for m in range(self.number_of_corrector_steps):
                 comp, _ = self._step(MDX_CORRECTOR, comp, 0, forces, 1 + m, d_index=d_index, in_place=True,

@@ -13,6 +13,13 @@ looked up on the live network at every use, never cached, so a network swapped o
   sigma_uniform_hint        set by uniform_sigma around a forward, read by the network's forward.  Absent: a plain call.
   logits_unread_hint        set by logits_unread around a forward whose atom-type logits nobody will read; the network may then
                             return A = None and leave out the work behind the logits.  Absent: a plain call.
+                            Given by the corrector steps that leave the types alone and, with ONE atom type, by the predictor
+                            steps too: the MASK logit is forced to -inf, and the type update makes the same of every
+                            (finite, -inf), so it runs without logits (mdx_pc_step_update, logits == NULL).  A difference in
+                            failure behaviour: non-finite node features in the LAST graph layer of such a forward no longer
+                            reach A (they fed the logits only; X never depended on them; the edge chain's own f16-range
+                            report is untouched).  Any recorder, forward hook or overridden _get_model_predictions, and any
+                            network with more than one atom type, keep the whole forward.
   capture_safe(B, N, dev)   the network's answer, asked by capture_safe.  Absent (True): the caller's use_hip_graph is believed.
   begin_f16_range_fallback  called by exact_f32 on entry.  Absent: no-op.
   adapt_f16_range           called by exact_f32 on exit.  Absent: no-op.
@@ -93,8 +100,8 @@ def outputs_watched(net) -> bool:
 
 @contextlib.contextmanager
 def logits_unread(net):
-    """Around a forward whose atom-type logits nobody reads (a corrector step that does not update the types, with nothing
-    recording or inspecting the predictions): the network may return A = None."""
+    """Around a forward whose atom-type logits nobody reads (a corrector step that does not update the types, or any step with
+    one atom type, with nothing recording or inspecting the predictions): the network may return A = None."""
     if not hasattr(net, "logits_unread_hint"):
         yield
         return

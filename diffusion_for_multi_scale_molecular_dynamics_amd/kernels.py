@@ -1544,10 +1544,21 @@ class NodeMlpPack(ChainPack):
                 all(l.in_features == H and l.out_features == H for l in layers[1:]) and all(l.bias is not None for l in layers))
 
 
-def node_mlp_rows(pack: NodeMlpPack, node_in, add_residual: bool, status=None, agg=None):
+def node_mlp_rows(pack: NodeMlpPack, node_in, add_residual: bool, status=None, agg=None, row_class=None):
     """(h if add_residual) + MLP([h | agg]) over the rows; with a pack built with next_projection: (out, out @
     next_projection.T [M, 2H]).  node_in [M, 2H] = [h | agg] (mdx_node_mlp_rows), or node_in = h [M, H] with agg [M, H] given
-    separately (mdx_node_mlp_rows_split: the concatenation is never formed)."""
+    separately (mdx_node_mlp_rows_split: the concatenation is never formed), or -- with row_class int64 [M] -- node_in =
+    class rows [n_classes, H] and h = node_in[row_class], never formed either (mdx_node_mlp_rows_indexed; a class outside
+    the rows: row 0 and MDX_STATUS_EGNN_TABLE in `status`)."""
+    if row_class is not None:
+        n_classes, W = node_in.shape
+        M = row_class.shape[0]
+        assert agg is not None and W == pack.hidden and tuple(agg.shape) == (M, W) and row_class.dtype == torch.int64
+        out = torch.empty(M, pack.hidden, dtype=F32, device=agg.device)
+        proj = torch.empty(M, 2 * pack.hidden, dtype=F32, device=agg.device) if pack.projects else None
+        call("mdx_node_mlp_rows_indexed", C.byref(pack.c_struct), node_in, n_classes, row_class, agg, int(bool(add_residual)), M,
+             None, out, proj, status)
+        return (out, proj) if pack.projects else out
     M, W = node_in.shape
     out = torch.empty(M, pack.hidden, dtype=F32, device=node_in.device)
     proj = torch.empty(M, 2 * pack.hidden, dtype=F32, device=node_in.device) if pack.projects else None
@@ -1743,12 +1754,14 @@ def egnn_table_gather(table, table_scalar, n_classes: int, n_even: int, atom_typ
     return out, coord_out
 
 
-def egnn_node_inputs(x, k_vectors, sigma, atom_types, emb_weight, emb_bias, second=None, memo: Optional[EgnnTableMemo] = None):
+def egnn_node_inputs(x, k_vectors, sigma, atom_types, emb_weight, emb_bias, second=None, memo: Optional[EgnnTableMemo] = None,
+                     with_h: bool = True):
     """z [n_nodes, 2 n_k] (torus uplift) and h [n_nodes, H] (embedding of [sigma | one_hot]) of EGNNScoreNetwork, one launch.
     x [B, N, 3] relative coordinates, sigma [B] (or [B,1]), atom_types [B, N] int64.
     second = (W2 [H2, F], b2 [H2]): a third output, the same input through that linear map (see mdx_egnn_node_inputs).
     memo: the launch on the class nodes of the first layer's distance grid (mdx_egnn_node_inputs_keyed) -- the outputs are the
-    memo's kept buffers, and the kernel returns at once while the memo's key holds the bits of sigma[0]."""
+    memo's kept buffers, and the kernel returns at once while the memo's key holds the bits of sigma[0].
+    with_h=False: h is neither allocated nor written (None in its place); z keeps its bits."""
     B, N, d = x.shape
     assert d == 3 and k_vectors.shape[1] == 3
     n_nodes, n_k, (H, F) = B * N, k_vectors.shape[0], emb_weight.shape
@@ -1761,7 +1774,7 @@ def egnn_node_inputs(x, k_vectors, sigma, atom_types, emb_weight, emb_bias, seco
             tuple(h2.shape) == (n_nodes, H2)
     else:
         z = torch.empty(n_nodes, 2 * n_k, dtype=F32, device=x.device)
-        h = torch.empty(n_nodes, H, dtype=F32, device=x.device)
+        h = torch.empty(n_nodes, H, dtype=F32, device=x.device) if with_h else None
         h2 = torch.empty(n_nodes, H2, dtype=F32, device=x.device) if second is not None else None
     call("mdx_egnn_node_inputs_keyed", x, k_vectors, n_k, sigma, N, atom_types, emb_weight, emb_bias, F, H, n_nodes, z, h, w2, b2,
          H2, h2, memo.key if memo is not None else None)

@@ -365,7 +365,8 @@ class E_GCL(nn.Module):
     def forward(self, h: torch.Tensor, edge_index: torch.Tensor, coord: torch.Tensor,
                 degree: Optional[torch.Tensor] = None, offsets: Optional[torch.Tensor] = None,
                 n_edges: Optional[torch.Tensor] = None, node_proj: Optional[torch.Tensor] = None,
-                next_layer: Optional["E_GCL"] = None, table=None, coords_only: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+                next_layer: Optional["E_GCL"] = None, table=None, coords_only: bool = False,
+                row_class: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """node_proj: this layer's per-node projections [n_nodes, 2H], when the previous layer's node kernel has already
         computed them; next_layer: the graph layer that follows (its projections are then computed by this layer's node
         kernel and left in self._next_proj).
@@ -378,7 +379,16 @@ class E_GCL(nn.Module):
         coords_only: the caller reads the coordinates alone (the last graph layer of a forward whose atom-type logits nobody
         reads: its h feeds the classification head only).  Where the layer runs the fused chain at full width without the
         attention gate, the message sums are then not gathered and the node MLP is not launched: (None, coord_out), the same
-        bits in coord_out.  Everywhere else the flag is ignored."""
+        bits in coord_out.  Everywhere else the flag is ignored.
+        row_class: int64 [n_nodes], with h = ONE row per class [n_classes, F] -- node i's features are h[row_class[i]], and the
+        [n_nodes, F] matrix does not exist.  Only with `table` and where class_rows_apply() holds (the caller asks first): the
+        layer then reads h in its node kernel alone, through the index."""
+        if row_class is not None:
+            pack = self._edge_chain_pack() if self.use_fused_ops and h.is_cuda and offsets is not None else None
+            if table is None or not self.class_rows_apply(pack, row_class.shape[0], h.shape[1], coord.shape[1], next_layer):
+                raise RuntimeError("E_GCL.forward: class rows were passed to a layer that does not run on the distance table")
+            return self._forward_edge_chain(pack, h, edge_index, coord.contiguous(), degree, offsets, n_edges, None, next_layer,
+                                            table, row_class=row_class)
         row, col = edge_index[:, 0], edge_index[:, 1]
         if degree is None:
             degree = torch.bincount(row, minlength=h.shape[0])
@@ -425,9 +435,22 @@ class E_GCL(nn.Module):
     def table_applies(self, pack, h, coord) -> bool:
         """Can the layer run on the distance grid (_table_gather)?  The chain's ROWS mode has no attention gate; the gather
         has the output contract of the node gather (full-width messages, H <= 256, D <= 8) and reports to the status word."""
+        return self.table_applies_to(pack, h.shape[0], h.shape[1], coord.shape[1])
+
+    def table_applies_to(self, pack, n_nodes: int, width: int, coord_dimension: int) -> bool:
+        """table_applies from the shapes alone (what a caller knows before it has made h)."""
         return (pack is not None and not self.attention and pack.piece_sums_ok and pack.message_width == pack.hidden
-                and pack.hidden <= 256 and h.shape[1] == pack.hidden and coord.shape[1] <= 8 and self.status_word is not None
-                and h.shape[0] < (1 << 31))
+                and pack.hidden <= 256 and width == pack.hidden and coord_dimension <= 8 and self.status_word is not None
+                and n_nodes < (1 << 31))
+
+    def class_rows_apply(self, pack, n_nodes: int, width: int, coord_dimension: int, next_layer=None) -> bool:
+        """May a caller whose h has one value per class pass the class rows and an index instead of h [n_nodes, H]
+        (forward's `row_class`)?  The layer must run on the distance table, where the edge part reads the classes and not h,
+        and its node MLP as the one launch that takes the index (kernels.node_mlp_rows).  Shapes and attributes only."""
+        if not self.table_applies_to(pack, n_nodes, width, coord_dimension):
+            return False
+        whole = self._node_mlp_pack(next_layer)
+        return whole is not None and whole.hidden == width
 
     def _table_gather(self, pack, table, left, coord, edge_index, offsets, degree):
         """egnn_node_gather's ([left | message sums] or the sums, coord_out) with the per-edge chain replaced by the chain on the
@@ -447,15 +470,15 @@ class E_GCL(nn.Module):
                                          flags=self._coord_flags(), status=self.status_word)
 
     def _forward_edge_chain(self, pack, h, edge_index, coord, degree, offsets, n_edges=None, node_proj=None, next_layer=None,
-                            table=None, coords_only=False):
+                            table=None, coords_only=False, row_class=None):
         """E_GCL.forward with the per-edge work in one MFMA kernel: node projections (library GEMM, per node) -> fused
         chain -> the two sorted-segment reductions -> node MLP.  With `table` (and table_applies) the per-edge chain and the
         node gather are _table_gather."""
         coord = coord.contiguous()
-        if table is not None and self.table_applies(pack, h, coord):
+        if table is not None and (row_class is not None or self.table_applies(pack, h, coord)):
             def gather(left):
                 return self._table_gather(pack, table, left, coord, edge_index, offsets, degree)
-            return self._node_part(h, gather, next_layer)
+            return self._node_part(h, gather, next_layer, row_class)
         proj = node_proj if node_proj is not None else torch.nn.functional.linear(h, pack.proj_weight)
         # the messages are added up per node inside the kernel (piece sums) and never written out as [E, H]
         in_kernel = pack.piece_sums_ok and h.shape[0] < (1 << 31)
@@ -488,8 +511,9 @@ class E_GCL(nn.Module):
             node_in = torch.cat([h, agg], dim=1)
         return self._node_mlp_tail(h, node_in, coord_out)
 
-    def _node_part(self, h, gather, next_layer):
-        """Everything per node after the per-edge work, from gather(left) -> ([left | message sums] or the sums, coord_out)."""
+    def _node_part(self, h, gather, next_layer, row_class=None):
+        """Everything per node after the per-edge work, from gather(left) -> ([left | message sums] or the sums, coord_out).
+        row_class: h holds one row per class (forward's `row_class`; class_rows_apply() has been asked)."""
         whole = self._node_mlp_pack(next_layer)
         if whole is not None and whole.hidden == h.shape[1]:
             # everything per node between the edge chain and the node MLP in one pass (the message sums and the updated
@@ -498,10 +522,11 @@ class E_GCL(nn.Module):
             # per-node projections: one launch on the matrix cores
             h = h.contiguous()
             agg, coord_out = gather(None)
-            out = kernels.node_mlp_rows(whole, h, self.residual, status=self.status_word, agg=agg)
+            out = kernels.node_mlp_rows(whole, h, self.residual, status=self.status_word, agg=agg, row_class=row_class)
             if whole.projects:
                 out, self._next_proj = out
             return out, coord_out
+        assert row_class is None
         node_in, coord_out = gather(h.contiguous())
         return self._node_mlp_tail(h, node_in, coord_out)
 
@@ -549,15 +574,18 @@ class EGNN(nn.Module):
 
     def forward(self, h: torch.Tensor, edges: torch.Tensor, x: torch.Tensor, degree=None, embedded: bool = False,
                 first_proj: Optional[torch.Tensor] = None, classify: bool = True, first_table=None,
-                coords_only: bool = False) -> AXL:
+                coords_only: bool = False, first_row_class: Optional[torch.Tensor] = None) -> AXL:
         """degree: None (a caller's own edge list, any order), the edge count per node [n_nodes] of a list sorted by source,
         or the triple (degree, offsets, n_edges) of a capacity-sized list (utils/neighbors.get_edges_static).
         embedded: h is already embedding_in(node features) (kernels.egnn_node_inputs); first_proj: the first graph layer's
         per-node projections [n_nodes, 2H] of that h, when the caller has them.  classify=False: A is the last layer's h (the
         caller applies node_classification_layer: kernels.egnn_outputs) and L is None.  first_table: kernels.EgnnTable for the
         first graph layer (E_GCL.forward's `table`).  coords_only (with classify=False): the caller reads X alone -- the last
-        graph layer gets E_GCL.forward's `coords_only`, and A is None when that layer could leave its node path out."""
+        graph layer gets E_GCL.forward's `coords_only`, and A is None when that layer could leave its node path out.
+        first_row_class (with embedded and first_table): h is one embedded row per class and this the nodes' classes -- the
+        first graph layer's `row_class`."""
         emb = self.embedding_in
+        assert first_row_class is None or (embedded and first_table is not None and len(self.graph_layers) > 0)
         if embedded:
             assert h.shape[1] == emb.out_features
         elif h.is_cuda and emb.in_features <= 8:
@@ -583,7 +611,8 @@ class EGNN(nn.Module):
         for k, layer in enumerate(self.graph_layers):
             following = self.graph_layers[k + 1] if k + 1 < len(self.graph_layers) else None
             h, x = layer(h, edges, x, degree, offsets, n_edges, node_proj=proj, next_layer=following,
-                         table=first_table if k == 0 else None, coords_only=coords_only and not classify and following is None)
+                         table=first_table if k == 0 else None, coords_only=coords_only and not classify and following is None,
+                         row_class=first_row_class if k == 0 else None)
             proj = layer.__dict__.pop("_next_proj", None)       # left there by the layer's node kernel, if it computed them
         if not classify:
             return AXL(A=h, X=x, L=None)

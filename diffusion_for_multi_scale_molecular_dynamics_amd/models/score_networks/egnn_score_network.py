@@ -136,6 +136,12 @@ class EGNNScoreNetwork(ScoreNetwork):
         # returns A = None; X keeps its bits.  False: the hint is ignored.
         self.skip_unread_logits = True
         self.logits_unread_hint = False
+        # Inside a sampler (sigma_uniform_hint) embedding_in([sigma | one_hot(A)]) has one value per class, and a first graph
+        # layer that runs on the distance table reads h in its node kernel alone.  That forward then makes neither h
+        # [n_nodes, H] nor the first layer's per-node projections: the node kernel reads the class rows the table's own grid
+        # problem has left in its memo (kernels.EgnnTableMemo.grid_h: mdx_egnn_node_inputs on one node per class at sigma[0])
+        # through the nodes' classes.  The same bits.  False: h is written per node, as before.
+        self.first_layer_class_rows = True
         self.egnn = self._make_egnn(hp)
 
     def __getstate__(self):
@@ -215,10 +221,9 @@ class EGNNScoreNetwork(ScoreNetwork):
             self._first_projection = (stamp, (w2, b2))
         return self._first_projection[1]
 
-    def _first_layer_table(self, edges, z, h, sigma, atom_types, k_vectors, second):
-        """kernels.EgnnTable for the first graph layer when first_layer_table selects it and the layer's shape allows it, else
-        None.  The grid problem's per-node projections are mdx_egnn_node_inputs' second output for one node per class at
-        sigma[0]: the arithmetic of the batch's own first_proj."""
+    def _table_serves_first_layer(self, n_edge_rows: int, n_nodes: int, coord_dimension: int) -> bool:
+        """Does first_layer_table select the distance table for a forward of this shape, and does the first graph layer's
+        shape allow it?  Shapes and attributes only: asked before the per-node inputs are made."""
         from ... import kernels
         mode = self.first_layer_table
         if mode not in ("auto", "on", "off"):
@@ -228,13 +233,36 @@ class EGNNScoreNetwork(ScoreNetwork):
             layer.reset_table_memos()                   # (a change of first_layer_table: the next table forward builds)
         self._table_mode_seen = mode
         if mode == "off" or (mode == "auto" and not self.sigma_uniform_hint):
+            return False
+        if not layer.table_applies_to(layer._edge_chain_pack(), n_nodes, self.egnn.embedding_in.out_features, coord_dimension):
+            return False
+        n_classes = self.num_atom_types + 1
+        n_even = kernels.egnn_table_points(coord_dimension)
+        return not (mode == "auto" and n_classes ** 2 * (2 * n_even - 1) * 8 > n_edge_rows)
+
+    def _class_rows_serve_first_layer(self, n_nodes: int, coord_dimension: int) -> bool:
+        """With the table serving the first layer: may the forward leave h [n_nodes, H] and the first projections unmade
+        (first_layer_class_rows)?  Only under the sampler's uniform-sigma hint -- a direct forward keeps its per-node h."""
+        layers = self.egnn.graph_layers
+        if not (self.first_layer_class_rows and self.sigma_uniform_hint):
+            return False
+        following = layers[1] if len(layers) > 1 else None
+        return layers[0].class_rows_apply(layers[0]._edge_chain_pack(), n_nodes, self.egnn.embedding_in.out_features,
+                                          coord_dimension, following)
+
+    def _first_layer_table(self, edges, z, h, sigma, atom_types, k_vectors, second, serves=None):
+        """kernels.EgnnTable for the first graph layer when first_layer_table selects it and the layer's shape allows it, else
+        None.  The grid problem's per-node projections are mdx_egnn_node_inputs' second output for one node per class at
+        sigma[0]: the arithmetic of the batch's own first_proj.  serves: _table_serves_first_layer's answer when the caller
+        has asked already (h may then be None: only z is looked at)."""
+        from ... import kernels
+        if serves is None:
+            serves = self._table_serves_first_layer(edges.shape[0], z.shape[0], z.shape[1])
+        if not serves:
             return None
-        if not layer.table_applies(layer._edge_chain_pack(), h, z):
-            return None
+        layer = self.egnn.graph_layers[0]
         n_classes = self.num_atom_types + 1
         n_even = kernels.egnn_table_points(z.shape[1])
-        if mode == "auto" and n_classes ** 2 * (2 * n_even - 1) * 8 > edges.shape[0]:
-            return None
         classes, _, _ = kernels.egnn_table_grid(n_classes, n_even, z.shape[1], z.device)
         G = classes.shape[0]
         grid_x = self.__dict__.get("_table_grid_x")
@@ -370,17 +398,27 @@ class EGNNScoreNetwork(ScoreNetwork):
             from ... import kernels
             k_vectors = self.bloch_wave_reciprocal_lattice_vectors.to(x)
             second = self._first_projection_of_inputs()
+            # what the first graph layer will run on is settled from shapes and attributes, BEFORE the per-node inputs: on the
+            # table, inside a sampler, it needs neither h nor its projections per node (first_layer_class_rows)
+            coord_dimension = 2 * k_vectors.shape[0]
+            serves = second is not None and self._table_serves_first_layer(edges.shape[0], bsz * n, coord_dimension)
+            class_rows = serves and self._class_rows_serve_first_layer(bsz * n, coord_dimension)
             res = kernels.egnn_node_inputs(x.contiguous(), k_vectors.contiguous(),
                                            sigma_in.to(device=x.device, dtype=torch.float32).reshape(-1).contiguous(),
                                            comp.A.reshape(bsz, n).long().contiguous(), emb.weight.detach().contiguous(),
-                                           emb.bias.detach().contiguous(), second=second)
-            z, h, first_proj = res if second is not None else (res[0], res[1], None)
-            table = self._first_layer_table(edges, z, h, sigma_in, comp.A, k_vectors, second) if second is not None else None
+                                           emb.bias.detach().contiguous(), second=None if class_rows else second,
+                                           with_h=not class_rows)
+            z, h, first_proj = res if len(res) == 3 else (res[0], res[1], None)
+            table = self._first_layer_table(edges, z, h, sigma_in, comp.A, k_vectors, second, serves=True) if serves else None
+            row_class = None
+            if class_rows:
+                h, row_class = table.memo.grid_h[:table.n_classes], table.atom_types
             head = self.egnn.node_classification_layer
             if head.out_features <= 8 and head.in_features % 4 == 0 and comp.L.dtype == torch.float32:
                 # classification layer (MASK logit at -inf), scores and the zero lattice output: one launch
                 out = self.egnn(h=h, edges=edges, x=z, degree=degree, embedded=True, first_proj=first_proj, classify=False,
-                                first_table=table, coords_only=self.skip_unread_logits and self.logits_unread_hint)
+                                first_table=table, coords_only=self.skip_unread_logits and self.logits_unread_hint,
+                                first_row_class=row_class)
                 if out.A is None:
                     scores = kernels.egnn_scores(z, out.X.contiguous(), k_vectors.contiguous())
                     return AXL(A=None, X=scores.reshape(bsz, n, d), L=torch.zeros_like(comp.L))
@@ -390,7 +428,8 @@ class EGNNScoreNetwork(ScoreNetwork):
                 logits = logits.reshape(bsz, n, -1)
                 logits._mdx_mask_imposed = True
                 return AXL(A=logits, X=scores.reshape(bsz, n, d), L=zeros.reshape(comp.L.shape))
-            out = self.egnn(h=h, edges=edges, x=z, degree=degree, embedded=True, first_proj=first_proj, first_table=table)
+            out = self.egnn(h=h, edges=edges, x=z, degree=degree, embedded=True, first_proj=first_proj, first_table=table,
+                            first_row_class=row_class)
             scores = kernels.egnn_scores(z, out.X.contiguous(), k_vectors.contiguous())
             return AXL(A=out.A.reshape(bsz, n, -1), X=scores.reshape(bsz, n, d), L=torch.zeros_like(comp.L))
 

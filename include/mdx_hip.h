@@ -205,7 +205,10 @@ MDX_API int mdx_atom_types_update(const float* logits, const int64_t* atom_types
  * corrector_step (:693-805) in ONE launch, scalars taken from the device-resident tables.
  * Pre-drawn noise (reference-RNG parity mode): z_coordinates [B,N,d], gumbel [B,N,C], u [B,N], z_lattice [B,nl];
  * any NULL pointer switches that draw to the device RNG (rng).  Outputs may alias inputs.
- * status (nullable): MDX_STATUS_MASK_AT_LAST_STEP is OR-ed in when index 1 leaves a MASK. */
+ * status (nullable): MDX_STATUS_MASK_AT_LAST_STEP is OR-ed in when index 1 leaves a MASK.
+ * logits == NULL with ONE atom type (num_classes == 2): every atom's logits are (0, -inf) -- what the update makes of any
+ * (finite, -inf), the only logits a score network can return there (the MASK logit is forced to -inf, and the clipped softmax
+ * of (l0, -inf) does not depend on a finite l0).  With more classes: MDX_ERR_INVALID_ARG. */
 MDX_API int mdx_pc_step_update(const mdx_schedule_t* sched_host, int mode, int index_i, const int32_t* d_index,
                        const mdx_pc_flags_t* flags_host, const int64_t* atom_types, const float* x, const float* l,
                        const float* logits, const float* score_x, const float* score_l, const float* z_coordinates,
@@ -1013,6 +1016,8 @@ MDX_API int mdx_egnn_table_gather(const float* table, const float* table_scalar,
  *                          (emb_weight [H, n_features] row-major, n_features = 2 + number of atom types; sigma [B] per
  *                          structure, atoms_per_structure nodes each; the same binary32 operations as the reference's).
  *                          An atom type outside [0, n_features - 2] contributes no column: h = b + sigma W[:,0];
+ *                          h_out nullable (a caller that keeps one row of h per class): z, and second_out when given,
+ *                          are written alone, with the same bits;
  *                          second_out (nullable, [n_nodes, second_width]): a second linear map of the same input,
  *                          b2 + sigma W2[:,0] + W2[:,1 + a] -- with W2 = P W, b2 = P b (formed by the caller) the first
  *                          graph layer's per-node projections P h without an [n_nodes,H] x [H,2H] product;
@@ -1056,6 +1061,15 @@ MDX_API int mdx_node_mlp_rows(const mdx_egnn_chain_t* chain_host, const float* n
 MDX_API int mdx_node_mlp_rows_split(const mdx_egnn_chain_t* chain_host, const float* h, const float* agg, int add_residual,
                                     int64_t n_rows, const int64_t* n_rows_dev, float* out, float* proj_out, uint32_t* status,
                                     mdx_stream_t stream);
+/* mdx_node_mlp_rows_split for an h with ONE value per class (the first graph layer inside a sampler: sigma is uniform over the
+ * batch, so embedding_in([sigma | one_hot(a)]) has n_classes distinct rows): class_rows [n_classes, H], row_class int64
+ * [n_rows]; row r's operand and residual are class_rows[row_class[r]] -- the [n_rows, H] matrix is neither written nor read.
+ * The same arithmetic, tile order and epilogue: out and proj_out have the bits of the split call on h = class_rows[row_class].
+ * A row_class outside [0, n_classes) reads row 0 and ORs MDX_STATUS_EGNN_TABLE into status (nullable); the call returns MDX_OK. */
+MDX_API int mdx_node_mlp_rows_indexed(const mdx_egnn_chain_t* chain_host, const float* class_rows, int n_classes,
+                                      const int64_t* row_class, const float* agg, int add_residual, int64_t n_rows,
+                                      const int64_t* n_rows_dev, float* out, float* proj_out, uint32_t* status,
+                                      mdx_stream_t stream);
 /* coord_out[i,:] = coord[i,:] + (1/degree_i if mean) sum_{e in segment i} (coord[i,:] - coord[dst_e,:]) edge_scalar[e]
  * -- E_GCL.coord_model's trans = coord_diff * coord_mlp(m), unsorted_segment_sum / _mean and the residual add
  * (models/egnn.py:162-200), on the sorted segments; no atomics, fixed summation order. */
