@@ -22,8 +22,42 @@ The HIP calls are invisible to autograd, so they are used only when no gradient 
 nothing requires grad); with autograd on, the module runs as plain PyTorch.  Callers that pass their own edge list
 (no `degree`) get it sorted by source here first: the segment kernels need that order, the reference's
 unsorted_segment_sum accepted any.
+
+What a layer launches is decided once per forward, by E_GCL.route() -> Route, and executed by E_GCL.run(): no other part of a
+forward asks for a pack or looks at a shape (inside route(), _node_mlp_pack asks for the next layer's edge pack, whose
+projection it appends).  `fused`: device tensors and no gradient can be requested; H: the chain's width; E: edge rows.
+The first row whose condition holds is taken:
+
+  edge part (RoutePath.edge)
+    "table"          the caller asks for it, and the chain applies, without attention, with in-kernel sums, at full message
+                     width, feature width == H <= 256, D <= 8, a status word, n_nodes < 2^31:
+                     [the grid's egnn_node_inputs, by the score network], egnn_edge_chain (keyed, on the grid),
+                     egnn_table_check, egnn_table_gather
+    "chain"          fused, offsets, E > 0, edge_chain_precision set, Linear / SiLU stacks of a width the kernel has (narrow or
+                     unequal widths zero-padded; attention only with in-kernel sums): [linear: the per-node projections, unless
+                     the previous layer's node kernel made them], egnn_edge_chain, then the reduction below
+    "torch"          otherwise: PyTorch -- with fused, message width % 4 == 0 and SiLU first, the first message layer is
+                     linear (per node) + egnn_message_input (RoutePath.message_input)
+  message sums (RoutePath.sums)
+    "table" / "pieces" / "rows"  by the table gather / inside the chain kernel as piece sums (the pack's LDS allows them,
+                     n_nodes < 2^31) / by segment_rows afterwards (chain without piece sums; PyTorch edge part with fused,
+                     offsets and message width % 4 == 0);   "torch": segment_reduce
+  per-node reductions (RoutePath.reduce)
+    "gather"         table, or chain with piece sums at full message width, feature width == H, D <= 8:
+                     ONE launch (egnn_table_gather / egnn_node_gather)
+    "aggregate"      any other chain: egnn_coord_aggregate, segment_combine (piece sums) or segment_rows, cat
+                     (RoutePath.sliced, a padded chain: the cat takes the sums' first message_width columns)
+    "coord_head"     PyTorch edge part with segment_rows and a plain H -> 1 head behind SiLU: egnn_coord_head;   "torch"
+  node part (RoutePath.node)
+    "none"           RoutePath.coords_only (asked for, chain + gather, no attention): the gather runs without its message half,
+                     h comes back None
+    "pack"           after a gather, a node MLP NodeMlpPack covers at the feature width: node_mlp_rows -- with the next
+                     layer's projections (RoutePath.projects_next) when that layer has a chain pack of the same width, and h
+                     read through the nodes' classes (RoutePath.class_rows) when asked for on the table
+    "rows"           RowChainPack covers the MLP after its first layer: linear + silu, mlp_chain_rows
+    "torch"          otherwise (always behind a PyTorch edge part)
 """
-from typing import Callable, Optional, Tuple
+from typing import Callable, List, NamedTuple, Optional, Tuple
 
 import torch
 from torch import nn
@@ -32,13 +66,32 @@ from .. import kernels
 from ..namespace import AXL
 
 
-def run_mlp(layers, x: torch.Tensor, fused: bool = False) -> torch.Tensor:
-    """Apply a Sequential of Linear / SiLU / ... modules as plain PyTorch ops (layer shapes the MFMA chains do not cover).
-    (`fused` is accepted for the callers' sake and ignored: rounds 1-4 ran every Linear + SiLU pair of this path as one
-    hipBLASLt matmul with a SWISH_BIAS epilogue; the library no longer links a vendor GEMM.)"""
+def run_mlp(layers, x: torch.Tensor) -> torch.Tensor:
+    """Apply a Sequential of Linear / SiLU / ... modules as plain PyTorch ops (layer shapes the MFMA chains do not cover)."""
     for layer in layers:
         x = layer(x)
     return x
+
+
+class RoutePath(NamedTuple):
+    """What one E_GCL forward launches, in plain words (the table in the module docstring)."""
+    edge: str                       # "torch" | "chain" | "table"
+    sums: str                       # "torch" | "rows" | "pieces" | "table"
+    reduce: str                     # "torch" | "coord_head" | "aggregate" | "gather"
+    sliced: bool = False
+    node: str = "torch"             # "torch" | "rows" | "pack" | "none"
+    coords_only: bool = False
+    class_rows: bool = False
+    projects_next: bool = False
+    message_input: bool = False
+
+
+class Route(NamedTuple):
+    """E_GCL.route()'s answer: the path and the packs it selected (node_pack: the NodeMlpPack of node == "pack", the
+    RowChainPack of "rows").  Good for the forward it was made for: the packs follow the parameters."""
+    path: RoutePath
+    edge_pack: Optional[kernels.EdgeChainPack] = None
+    node_pack: Optional[kernels.ChainPack] = None
 
 
 def segment_sum_sorted(data: torch.Tensor, degree: torch.Tensor) -> torch.Tensor:
@@ -205,7 +258,8 @@ class E_GCL(nn.Module):
         for memo in self.device_state.memos.values():
             memo.reset()
 
-    def _messages(self, h: torch.Tensor, edge_index: torch.Tensor, radial: torch.Tensor, fused: bool) -> torch.Tensor:
+    def _messages(self, h: torch.Tensor, edge_index: torch.Tensor, radial: torch.Tensor, message_input: bool) -> torch.Tensor:
+        """The message MLP in PyTorch; message_input (RoutePath's): its first layer and SiLU as kernels.egnn_message_input."""
         first = self.message_mlp[0]
         n_in = self.input_size
         w = first.weight
@@ -213,7 +267,7 @@ class E_GCL(nn.Module):
         # node-level projections h W_src^T | h W_dst^T, combined per edge
         proj = torch.nn.functional.linear(h, torch.cat([w[:, :n_in], w[:, n_in:2 * n_in]], dim=0))
         rest = list(self.message_mlp)[1:]
-        if fused and mh % 4 == 0 and isinstance(rest[0], nn.SiLU):
+        if message_input:
             out = kernels.egnn_message_input(proj.contiguous(), edge_index, radial.reshape(-1).contiguous(), first.bias,
                                              w[:, 2 * n_in].contiguous(), silu=True)
             rest = rest[1:]
@@ -221,7 +275,7 @@ class E_GCL(nn.Module):
             row, col = edge_index[:, 0], edge_index[:, 1]
             pre = proj[:, :mh].index_select(0, row) + proj[:, mh:].index_select(0, col)
             out = torch.addcmul(pre + first.bias, radial, w[:, 2 * n_in].unsqueeze(0))
-        out = run_mlp(rest, out, fused)
+        out = run_mlp(rest, out)
         if self.attention:
             out = out * self.att_mlp(out)
         return out
@@ -367,90 +421,66 @@ class E_GCL(nn.Module):
                 n_edges: Optional[torch.Tensor] = None, node_proj: Optional[torch.Tensor] = None,
                 next_layer: Optional["E_GCL"] = None, table=None, coords_only: bool = False,
                 row_class: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """node_proj: this layer's per-node projections [n_nodes, 2H], when the previous layer's node kernel has already
-        computed them; next_layer: the graph layer that follows (its projections are then computed by this layer's node
-        kernel and left in self._next_proj).
-        h [n_nodes, F]; edge_index [E, 2] sorted by column 0; coord [n_nodes, D]; degree [n_nodes] edge counts;
+        """h [n_nodes, F]; edge_index [E, 2] sorted by column 0; coord [n_nodes, D]; degree [n_nodes] edge counts;
         offsets [n_nodes] = exclusive scan of degree (enables the segment kernels on device tensors); n_edges: int64 [1]
         on the device when edge_index is a capacity-sized list whose first n_edges rows are the edges (fused chain only);
+        node_proj: this layer's per-node projections [n_nodes, 2H], when the previous layer's node kernel has already
+        computed them; next_layer: the graph layer that follows (run() returns its projections when this layer's node
+        kernel computes them; they are dropped here).
+        table, coords_only, row_class: what the caller would like (route()); a table or a coords_only that the layer cannot
+        honour is ignored, class rows it cannot honour are an error (there is no h per node to fall back to):
         table: kernels.EgnnTable when the caller guarantees what the layer's per-edge output on a distance grid needs (one
         value of h per class, the coordinates a torus uplift): the edge chain then runs on the grid and the edges are
         interpolated from it (_table_gather).
         coords_only: the caller reads the coordinates alone (the last graph layer of a forward whose atom-type logits nobody
-        reads: its h feeds the classification head only).  Where the layer runs the fused chain at full width without the
-        attention gate, the message sums are then not gathered and the node MLP is not launched: (None, coord_out), the same
-        bits in coord_out.  Everywhere else the flag is ignored.
+        reads: its h feeds the classification head only): (None, coord_out), the same bits in coord_out.
         row_class: int64 [n_nodes], with h = ONE row per class [n_classes, F] -- node i's features are h[row_class[i]], and the
-        [n_nodes, F] matrix does not exist.  Only with `table` and where class_rows_apply() holds (the caller asks first): the
-        layer then reads h in its node kernel alone, through the index."""
-        if row_class is not None:
-            pack = self._edge_chain_pack() if self.use_fused_ops and h.is_cuda and offsets is not None else None
-            if table is None or not self.class_rows_apply(pack, row_class.shape[0], h.shape[1], coord.shape[1], next_layer):
-                raise RuntimeError("E_GCL.forward: class rows were passed to a layer that does not run on the distance table")
-            return self._forward_edge_chain(pack, h, edge_index, coord.contiguous(), degree, offsets, n_edges, None, next_layer,
-                                            table, row_class=row_class)
-        row, col = edge_index[:, 0], edge_index[:, 1]
+        [n_nodes, F] matrix does not exist: the layer reads h in its node kernel alone, through the index."""
         if degree is None:
-            degree = torch.bincount(row, minlength=h.shape[0])
+            degree = torch.bincount(edge_index[:, 0], minlength=h.shape[0])
         # the HIP calls are invisible to autograd: only when no gradient can be requested
         needs_grad = torch.is_grad_enabled() and (h.requires_grad or coord.requires_grad or
                                                   any(t.requires_grad for t in self.parameters()))
-        fused = self.use_fused_ops and h.is_cuda and not needs_grad
-        if fused and offsets is not None and edge_index.shape[0] > 0:
-            pack = self._edge_chain_pack()
-            if pack is not None:
-                return self._forward_edge_chain(pack, h, edge_index, coord, degree, offsets, n_edges, node_proj, next_layer,
-                                                table, coords_only)
-        assert n_edges is None, "a capacity-sized edge list needs the fused edge chain in every layer"
-        count = degree.clamp(min=1).to(h.dtype).unsqueeze(1)      # (the reference DIVIDES by the count: egnn_utils.py:66-68)
-
-        coord_diff = coord.index_select(0, row) - coord.index_select(0, col)
-        radial = (coord_diff ** 2).sum(dim=1, keepdim=True)
-        if self.normalize:
-            coord_diff = torch.tanh(radial) / torch.sqrt(radial + self.epsilon ** 2) * coord_diff
-
-        messages = self._messages(h, edge_index, radial, fused)
-
-        segments = fused and offsets is not None and messages.shape[1] % 4 == 0
-        if segments and self._coord_head_is_plain():
-            hidden = run_mlp(list(self.coord_mlp)[:-1], messages, fused)
-            coord = coord + kernels.egnn_coord_head(hidden.contiguous(), self.coord_mlp[-1].weight.reshape(-1),
-                                                    coord_diff.contiguous(), offsets, degree, self.coords_mean)
-        else:
-            trans = segment_sum_sorted(coord_diff * run_mlp(self.coord_mlp, messages, fused), degree)
-            coord = coord + (trans / count if self.coords_mean else trans)
-
-        if segments:
-            agg = kernels.segment_rows(messages.contiguous(), offsets, degree, self.message_mean)
-        else:
-            agg = segment_sum_sorted(messages, degree)
-            if self.message_mean:
-                agg = agg / count
-        out = run_mlp(self.node_mlp, torch.cat([h, agg], dim=1), fused)
-        if self.residual:
-            out = h + out
+        route = self.route(degree.shape[0], h.shape[1], coord.shape[1], edge_index.shape[0], h.is_cuda and not needs_grad,
+                           offsets is not None, next_layer, table is not None, coords_only, row_class is not None)
+        out, coord, _ = self.run(route, h, edge_index, coord, degree, offsets, n_edges, node_proj, table, row_class)
         return out, coord
 
-
-    def table_applies(self, pack, h, coord) -> bool:
-        """Can the layer run on the distance grid (_table_gather)?  The chain's ROWS mode has no attention gate; the gather
-        has the output contract of the node gather (full-width messages, H <= 256, D <= 8) and reports to the status word."""
-        return self.table_applies_to(pack, h.shape[0], h.shape[1], coord.shape[1])
-
-    def table_applies_to(self, pack, n_nodes: int, width: int, coord_dimension: int) -> bool:
-        """table_applies from the shapes alone (what a caller knows before it has made h)."""
-        return (pack is not None and not self.attention and pack.piece_sums_ok and pack.message_width == pack.hidden
-                and pack.hidden <= 256 and width == pack.hidden and coord_dimension <= 8 and self.status_word is not None
-                and n_nodes < (1 << 31))
-
-    def class_rows_apply(self, pack, n_nodes: int, width: int, coord_dimension: int, next_layer=None) -> bool:
-        """May a caller whose h has one value per class pass the class rows and an index instead of h [n_nodes, H]
-        (forward's `row_class`)?  The layer must run on the distance table, where the edge part reads the classes and not h,
-        and its node MLP as the one launch that takes the index (kernels.node_mlp_rows).  Shapes and attributes only."""
-        if not self.table_applies_to(pack, n_nodes, width, coord_dimension):
-            return False
-        whole = self._node_mlp_pack(next_layer)
-        return whole is not None and whole.hidden == width
+    def route(self, n_nodes: int, width: int, coord_dimension: int, n_edge_rows: int, fused: bool, has_offsets: bool,
+              next_layer: Optional["E_GCL"] = None, table: bool = False, coords_only: bool = False,
+              class_rows: bool = False) -> Route:
+        """What a forward of this shape runs (the table in the module docstring), from shapes and attributes alone: the one
+        place that asks for the layer's packs and evaluates what they and the kernels cover.
+        width: h's; fused: device tensors and no gradient can be requested; has_offsets: forward's `offsets` are there;
+        table, coords_only, class_rows: the caller's wishes -- granted where the table says so, else dropped: read the answer
+        in the path (a caller with class rows asks BEFORE it decides not to make h per node)."""
+        fused = fused and self.use_fused_ops
+        pack = self._edge_chain_pack() if fused and has_offsets and n_edge_rows > 0 else None
+        if pack is None:
+            linears = [m for m in self.message_mlp if isinstance(m, nn.Linear)]
+            message_input = fused and linears[0].out_features % 4 == 0 and isinstance(self.message_mlp[1], nn.SiLU)
+            segments = fused and has_offsets and linears[-1].out_features % 4 == 0
+            return Route(RoutePath("torch", "rows" if segments else "torch",
+                              "coord_head" if segments and self._coord_head_is_plain() else "torch", message_input=message_input))
+        pieces = pack.piece_sums_ok and n_nodes < (1 << 31)     # the messages are added up per node inside the kernel
+        full = pack.message_width == pack.hidden                # (else a narrow / unequal-width layer run zero-padded)
+        gather_covers = pieces and full and width == pack.hidden and coord_dimension <= 8
+        # the chain's ROWS mode has no attention gate; the table gather has the node gather's output contract and reports
+        # to the status word
+        on_table = table and gather_covers and not self.attention and pack.hidden <= 256 and self.status_word is not None
+        edge, sums = ("table", "table") if on_table else ("chain", "pieces" if pieces else "rows")
+        if gather_covers and coords_only and not on_table and not self.attention:
+            return Route(RoutePath(edge, sums, "gather", node="none", coords_only=True), pack)
+        whole = self._node_mlp_pack(next_layer) if gather_covers else None
+        if whole is not None and whole.hidden == width:
+            return Route(RoutePath(edge, sums, "gather", node="pack", class_rows=class_rows and on_table,
+                              projects_next=whole.projects), pack, whole)
+        # the node MLP on [h | agg] as one matrix: its first layer in PyTorch, the rest as one launch where a pack covers it
+        rows = self._node_chain_pack()
+        if rows is not None and self.residual and width != rows.hidden:
+            rows = None
+        return Route(RoutePath(edge, sums, "gather" if gather_covers else "aggregate", not full,
+                          node="torch" if rows is None else "rows"), pack, rows)
 
     def _table_gather(self, pack, table, left, coord, edge_index, offsets, degree):
         """egnn_node_gather's ([left | message sums] or the sums, coord_out) with the per-edge chain replaced by the chain on the
@@ -469,81 +499,94 @@ class E_GCL(nn.Module):
                                          self.message_mean, left, coord, edge_index, self.coords_mean,
                                          flags=self._coord_flags(), status=self.status_word)
 
-    def _forward_edge_chain(self, pack, h, edge_index, coord, degree, offsets, n_edges=None, node_proj=None, next_layer=None,
-                            table=None, coords_only=False, row_class=None):
-        """E_GCL.forward with the per-edge work in one MFMA kernel: node projections (library GEMM, per node) -> fused
-        chain -> the two sorted-segment reductions -> node MLP.  With `table` (and table_applies) the per-edge chain and the
-        node gather are _table_gather."""
+    def run(self, route: Route, h, edge_index, coord, degree, offsets=None, n_edges=None, node_proj=None, table=None,
+            row_class=None):
+        """forward() on `route` (this layer's, for these shapes) -> (h_out, or None with coords_only; coord_out; the next
+        layer's per-node projections, or None).  The arguments are forward()'s."""
+        path, pack = route.path, route.edge_pack
+        assert (row_class is not None) == path.class_rows, "class rows go to a layer whose route reads them, and only there"
+        if pack is None:
+            return self._run_torch(path, h, edge_index, coord, degree, offsets, n_edges) + (None,)
         coord = coord.contiguous()
-        if table is not None and (row_class is not None or self.table_applies(pack, h, coord)):
+        n_rows, flags = edge_index.shape[0], self._coord_flags()
+        if path.edge == "table":
             def gather(left):
                 return self._table_gather(pack, table, left, coord, edge_index, offsets, degree)
-            return self._node_part(h, gather, next_layer, row_class)
-        proj = node_proj if node_proj is not None else torch.nn.functional.linear(h, pack.proj_weight)
-        # the messages are added up per node inside the kernel (piece sums) and never written out as [E, H]
-        in_kernel = pack.piece_sums_ok and h.shape[0] < (1 << 31)
-        messages, edge_scalar = kernels.egnn_edge_chain(pack, proj.contiguous(), coord, edge_index, status=self.status_word,
-                                                        n_edges_dev=n_edges, piece_sums=in_kernel)
-        padded = pack.message_width != pack.hidden      # a narrow / unequal-width layer run zero-padded (kernels.EdgeChainPack)
-        if padded:
-            # the message sums come out [n_nodes, H] with columns message_width .. H-1 zero: the node MLP takes the real ones
-            coord_out = kernels.egnn_coord_aggregate(edge_scalar, coord, edge_index, offsets, degree, self.coords_mean,
-                                                     flags=self._coord_flags())
-            agg = (kernels.segment_combine(messages, edge_index.shape[0], offsets, degree, self.message_mean) if in_kernel
-                   else kernels.segment_rows(messages, offsets, degree, self.message_mean))
-            node_in = torch.cat([h, agg[:, :pack.message_width]], dim=1)
-        elif in_kernel and h.shape[1] == messages.shape[1] and coord.shape[1] <= 8:
-            if coords_only and not self.attention:
+        else:
+            # node projections (a PyTorch matmul per node) -> the per-edge work in one MFMA kernel; with piece sums the
+            # messages are added up per node inside the kernel and never written out as [E, H]
+            proj = node_proj if node_proj is not None else torch.nn.functional.linear(h, pack.proj_weight)
+            pieces = path.sums == "pieces"
+            messages, edge_scalar = kernels.egnn_edge_chain(pack, proj.contiguous(), coord, edge_index, status=self.status_word,
+                                                            n_edges_dev=n_edges, piece_sums=pieces)
+            if path.coords_only:
                 # the coordinate half of the node gather alone (the same launch with the message half switched off: the same
                 # butterfly, the same bits); no node MLP
-                return kernels.egnn_node_gather(None, edge_index.shape[0], offsets, degree, self.message_mean, None, edge_scalar,
-                                                coord, edge_index, self.coords_mean, flags=self._coord_flags())
+                return kernels.egnn_node_gather(None, n_rows, offsets, degree, self.message_mean, None, edge_scalar, coord,
+                                                edge_index, self.coords_mean, flags=flags) + (None,)
 
             def gather(left):
-                return kernels.egnn_node_gather(messages, edge_index.shape[0], offsets, degree, self.message_mean, left,
-                                                edge_scalar, coord, edge_index, self.coords_mean, flags=self._coord_flags())
-            return self._node_part(h, gather, next_layer)
-        else:
-            coord_out = kernels.egnn_coord_aggregate(edge_scalar, coord, edge_index, offsets, degree, self.coords_mean,
-                                                     flags=self._coord_flags())
-            agg = (kernels.segment_combine(messages, edge_index.shape[0], offsets, degree, self.message_mean) if in_kernel
-                   else kernels.segment_rows(messages, offsets, degree, self.message_mean))
-            node_in = torch.cat([h, agg], dim=1)
-        return self._node_mlp_tail(h, node_in, coord_out)
-
-    def _node_part(self, h, gather, next_layer, row_class=None):
-        """Everything per node after the per-edge work, from gather(left) -> ([left | message sums] or the sums, coord_out).
-        row_class: h holds one row per class (forward's `row_class`; class_rows_apply() has been asked)."""
-        whole = self._node_mlp_pack(next_layer)
-        if whole is not None and whole.hidden == h.shape[1]:
+                if path.reduce == "gather":
+                    return kernels.egnn_node_gather(messages, n_rows, offsets, degree, self.message_mean, left, edge_scalar,
+                                                    coord, edge_index, self.coords_mean, flags=flags)
+                coord_out = kernels.egnn_coord_aggregate(edge_scalar, coord, edge_index, offsets, degree, self.coords_mean,
+                                                         flags=flags)
+                agg = (kernels.segment_combine(messages, n_rows, offsets, degree, self.message_mean) if pieces
+                       else kernels.segment_rows(messages, offsets, degree, self.message_mean))
+                if path.sliced:     # [n_nodes, H] with columns message_width .. H-1 zero: the node MLP takes the real ones
+                    agg = agg[:, :pack.message_width]
+                return torch.cat([left, agg], dim=1), coord_out
+        if path.node == "pack":
             # everything per node between the edge chain and the node MLP in one pass (the message sums and the updated
             # coordinates), then the whole node MLP (its 2H -> H layer included, reading h and the sums as the two halves of
             # its input row: [h | agg] is never formed), the residual and -- when a graph layer follows -- that layer's
             # per-node projections: one launch on the matrix cores
             h = h.contiguous()
             agg, coord_out = gather(None)
-            out = kernels.node_mlp_rows(whole, h, self.residual, status=self.status_word, agg=agg, row_class=row_class)
-            if whole.projects:
-                out, self._next_proj = out
-            return out, coord_out
-        assert row_class is None
+            out = kernels.node_mlp_rows(route.node_pack, h, self.residual, status=self.status_word, agg=agg, row_class=row_class)
+            out, next_proj = out if path.projects_next else (out, None)
+            return out, coord_out, next_proj
         node_in, coord_out = gather(h.contiguous())
-        return self._node_mlp_tail(h, node_in, coord_out)
-
-    def _node_mlp_tail(self, h, node_in, coord_out):
-        """The node MLP on node_in = [h | agg] and the residual."""
-        node_pack = self._node_chain_pack()
-        if node_pack is not None and (not self.residual or h.shape[1] == node_pack.hidden):
+        if path.node == "rows":
             # first node layer (2H -> H, + SiLU): a PyTorch matmul per node; the other layers and the residual: one MFMA launch
             first = self.node_mlp[0]
             hidden = torch.nn.functional.silu(torch.nn.functional.linear(node_in, first.weight, first.bias))
-            out = kernels.mlp_chain_rows(node_pack, hidden, residual=h.contiguous() if self.residual else None,
+            out = kernels.mlp_chain_rows(route.node_pack, hidden, residual=h.contiguous() if self.residual else None,
                                          status=self.status_word)
-            return out, coord_out
-        out = run_mlp(self.node_mlp, node_in, True)
-        if self.residual:
-            out = h + out
-        return out, coord_out
+            return out, coord_out, None
+        out = run_mlp(self.node_mlp, node_in)
+        return (h + out if self.residual else out), coord_out, None
+
+    def _run_torch(self, path: RoutePath, h, edge_index, coord, degree, offsets, n_edges):
+        """run() without an edge chain: PyTorch, any shape, differentiable -- but for the three helper kernels the path names
+        (only ever where no gradient can be requested)."""
+        assert n_edges is None, "a capacity-sized edge list needs the fused edge chain in every layer"
+        row, col = edge_index[:, 0], edge_index[:, 1]
+        count = degree.clamp(min=1).to(h.dtype).unsqueeze(1)      # (the reference DIVIDES by the count: egnn_utils.py:66-68)
+
+        coord_diff = coord.index_select(0, row) - coord.index_select(0, col)
+        radial = (coord_diff ** 2).sum(dim=1, keepdim=True)
+        if self.normalize:
+            coord_diff = torch.tanh(radial) / torch.sqrt(radial + self.epsilon ** 2) * coord_diff
+
+        messages = self._messages(h, edge_index, radial, path.message_input)
+
+        if path.reduce == "coord_head":
+            hidden = run_mlp(list(self.coord_mlp)[:-1], messages)
+            coord = coord + kernels.egnn_coord_head(hidden.contiguous(), self.coord_mlp[-1].weight.reshape(-1),
+                                                    coord_diff.contiguous(), offsets, degree, self.coords_mean)
+        else:
+            trans = segment_sum_sorted(coord_diff * run_mlp(self.coord_mlp, messages), degree)
+            coord = coord + (trans / count if self.coords_mean else trans)
+
+        if path.sums == "rows":
+            agg = kernels.segment_rows(messages.contiguous(), offsets, degree, self.message_mean)
+        else:
+            agg = segment_sum_sorted(messages, degree)
+            if self.message_mean:
+                agg = agg / count
+        out = run_mlp(self.node_mlp, torch.cat([h, agg], dim=1))
+        return (h + out if self.residual else out), coord
 
 
 class EGNN(nn.Module):
@@ -572,23 +615,59 @@ class EGNN(nn.Module):
                 act_fn=act_fn, residual=residual, attention=attention, normalize=normalize, coords_agg=coords_agg,
                 message_agg=message_agg, tanh=tanh))
 
-    def forward(self, h: torch.Tensor, edges: torch.Tensor, x: torch.Tensor, degree=None, embedded: bool = False,
-                first_proj: Optional[torch.Tensor] = None, classify: bool = True, first_table=None,
-                coords_only: bool = False, first_row_class: Optional[torch.Tensor] = None) -> AXL:
+    def routes(self, n_nodes: int, coord_dimension: int, n_edge_rows: int, fused, has_offsets: bool, table: bool = False,
+               coords_only: bool = False, class_rows: bool = False) -> List[Route]:
+        """Every graph layer's E_GCL.route() for a forward of these shapes, each with the layer behind it as its next_layer.
+        fused: device tensors and no gradient can be requested -- one answer, or one per layer; table, class_rows: wishes for
+        the FIRST layer (it runs on a distance table; h is one row per class); coords_only: for the LAST (nobody reads h)."""
+        layers = list(self.graph_layers)
+        fused = list(fused) if isinstance(fused, (list, tuple)) else [fused] * len(layers)
+        return [layer.route(n_nodes, self.embedding_in.out_features, coord_dimension, n_edge_rows, fused[k], has_offsets,
+                            following, table and k == 0, coords_only and following is None, class_rows and k == 0)
+                for k, (layer, following) in enumerate(zip(layers, layers[1:] + [None]))]
+
+    def run(self, routes: List[Route], h: torch.Tensor, edges: torch.Tensor, x: torch.Tensor, degree, first_proj=None,
+            first_table=None, first_row_class=None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+        """The graph layers on `routes` (routes() for these shapes) -> (h, or None when the last route is coords_only; x).
+        h: embedding_in(node features) already (kernels.egnn_node_inputs); degree: the edge count per node [n_nodes] of a list
+        sorted by source, or the triple (degree, offsets, n_edges) of a capacity-sized list (utils/neighbors.get_edges_static).
+        For the first layer, where the caller has them: first_proj, its per-node projections [n_nodes, 2H] of h; first_table,
+        the kernels.EgnnTable of a "table" route; first_row_class, the nodes' classes of a class_rows route, h then being one
+        embedded row per class (E_GCL.forward's node_proj, table and row_class)."""
+        n_edges = None
+        if isinstance(degree, tuple):
+            degree, offsets, n_edges = degree
+        else:
+            offsets = (torch.cumsum(degree, 0) - degree) if x.is_cuda else None
+        proj, table, row_class = first_proj, first_table, first_row_class
+        for layer, route in zip(self.graph_layers, routes):
+            h, x, proj = layer.run(route, h, edges, x, degree, offsets, n_edges, proj, table, row_class)
+            table = row_class = None
+        return h, x
+
+    def no_gradient_reaches(self, h: torch.Tensor, x: torch.Tensor) -> List[bool]:
+        """Per graph layer: can no gradient be requested through it?  None comes in with h or x, and neither it nor a layer
+        before it has a parameter that asks for one (the HIP calls are invisible to autograd)."""
+        grad, free = torch.is_grad_enabled(), []
+        reached = grad and (h.requires_grad or x.requires_grad)
+        for layer in self.graph_layers:
+            reached = reached or (grad and any(t.requires_grad for t in layer.parameters()))
+            free.append(not reached)
+        return free
+
+    def forward(self, h: torch.Tensor, edges: torch.Tensor, x: torch.Tensor, degree=None, routes: Optional[List[Route]] = None,
+                first_proj=None, first_table=None, first_row_class=None) -> AXL:
         """degree: None (a caller's own edge list, any order), the edge count per node [n_nodes] of a list sorted by source,
         or the triple (degree, offsets, n_edges) of a capacity-sized list (utils/neighbors.get_edges_static).
-        embedded: h is already embedding_in(node features) (kernels.egnn_node_inputs); first_proj: the first graph layer's
-        per-node projections [n_nodes, 2H] of that h, when the caller has them.  classify=False: A is the last layer's h (the
-        caller applies node_classification_layer: kernels.egnn_outputs) and L is None.  first_table: kernels.EgnnTable for the
-        first graph layer (E_GCL.forward's `table`).  coords_only (with classify=False): the caller reads X alone -- the last
-        graph layer gets E_GCL.forward's `coords_only`, and A is None when that layer could leave its node path out.
-        first_row_class (with embedded and first_table): h is one embedded row per class and this the nodes' classes -- the
-        first graph layer's `row_class`."""
+        routes: the score network's entrance (a module call, so that forward hooks see it) -- run() with these arguments, on
+        inputs it has prepared: A is the last layer's h (the caller applies node_classification_layer: kernels.egnn_outputs),
+        L is None."""
+        if routes is not None:
+            h, x = self.run(routes, h, edges, x, degree, first_proj, first_table, first_row_class)
+            return AXL(A=h, X=x, L=None)
+        assert first_proj is None and first_table is None and first_row_class is None, "prepared inputs come with routes"
         emb = self.embedding_in
-        assert first_row_class is None or (embedded and first_table is not None and len(self.graph_layers) > 0)
-        if embedded:
-            assert h.shape[1] == emb.out_features
-        elif h.is_cuda and emb.in_features <= 8:
+        if h.is_cuda and emb.in_features <= 8:
             # [sigma | one-hot type] -> hidden: with 2-4 input features the library GEMM spends 0.45 ms on a K = 3
             # problem; as rank-1 updates it is a few elementwise passes over [n_nodes, hidden]
             out = emb.bias.unsqueeze(0) + h[:, :1] * emb.weight[:, 0].unsqueeze(0)
@@ -602,18 +681,6 @@ class EGNN(nn.Module):
             # kernels need the edges grouped by source, so sort them (stable: the order within a node is kept)
             edges = edges[torch.argsort(edges[:, 0], stable=True)]
             degree = torch.bincount(edges[:, 0], minlength=h.shape[0])
-        n_edges = None
-        if isinstance(degree, tuple):
-            degree, offsets, n_edges = degree
-        else:
-            offsets = (torch.cumsum(degree, 0) - degree) if h.is_cuda else None
-        proj = first_proj
-        for k, layer in enumerate(self.graph_layers):
-            following = self.graph_layers[k + 1] if k + 1 < len(self.graph_layers) else None
-            h, x = layer(h, edges, x, degree, offsets, n_edges, node_proj=proj, next_layer=following,
-                         table=first_table if k == 0 else None, coords_only=coords_only and not classify and following is None,
-                         row_class=first_row_class if k == 0 else None)
-            proj = layer.__dict__.pop("_next_proj", None)       # left there by the layer's node kernel, if it computed them
-        if not classify:
-            return AXL(A=h, X=x, L=None)
+        fused = [h.is_cuda and free for free in self.no_gradient_reaches(h, x)]
+        h, x = self.run(self.routes(h.shape[0], x.shape[1], edges.shape[0], fused, x.is_cuda), h, edges, x, degree)
         return AXL(A=self.node_classification_layer(h), X=x, L=torch.zeros_like(x))

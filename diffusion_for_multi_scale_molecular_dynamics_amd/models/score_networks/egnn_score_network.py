@@ -199,16 +199,21 @@ class EGNNScoreNetwork(ScoreNetwork):
         if output.A is not None and not getattr(output.A, "_mdx_mask_imposed", False):
             super()._impose_non_mask_atomic_type_prediction(output)
 
-    def _first_projection_of_inputs(self):
+    def _routes(self, n_nodes: int, coord_dimension: int, n_edge_rows: int, **wishes):
+        """EGNN.routes for the fused forward (device tensors, no autograd, offsets from the graph builder)."""
+        return self.egnn.routes(n_nodes, coord_dimension, n_edge_rows, True, True, **wishes)
+
+    def _first_projection_of_inputs(self, pack=None):
         """(P W_emb, P b_emb) for the first graph layer's per-node projection matrix P = [W_src; W_dst]: the projections of
         the embedded inputs are then a linear map of [sigma | one_hot] like the embedding itself (no [n_nodes, H] x [H, 2H]
         product per forward).  None when the first layer does not run the fused edge chain.  Cached on the parameters'
-        versions."""
+        versions.  pack: the first route's edge pack (P's owner); a caller without a route leaves it out."""
         from ... import kernels
         layers = self.egnn.graph_layers
         if len(layers) == 0 or not layers[0].use_fused_ops:
             return None
-        pack = layers[0]._edge_chain_pack()
+        if pack is None:
+            pack = layers[0]._edge_chain_pack()
         emb = self.egnn.embedding_in
         if pack is None or pack.proj_weight.shape[1] != emb.out_features:
             return None
@@ -221,44 +226,37 @@ class EGNNScoreNetwork(ScoreNetwork):
             self._first_projection = (stamp, (w2, b2))
         return self._first_projection[1]
 
-    def _table_serves_first_layer(self, n_edge_rows: int, n_nodes: int, coord_dimension: int) -> bool:
-        """Does first_layer_table select the distance table for a forward of this shape, and does the first graph layer's
-        shape allow it?  Shapes and attributes only: asked before the per-node inputs are made."""
+    def _table_serves_first_layer(self, n_edge_rows: int, coord_dimension: int) -> bool:
+        """Does first_layer_table select the distance table for a forward of this shape?  The network's policy alone, a wish
+        for the first graph layer's route: whether that layer's shape allows the table is the route's answer."""
         from ... import kernels
         mode = self.first_layer_table
         if mode not in ("auto", "on", "off"):
             raise ValueError(f"first_layer_table should be auto, on or off. Got {mode}")
-        layer = self.egnn.graph_layers[0]
-        if mode != self.__dict__.get("_table_mode_seen", mode):
-            layer.reset_table_memos()                   # (a change of first_layer_table: the next table forward builds)
+        if mode != self.__dict__.get("_table_mode_seen", mode) and len(self.egnn.graph_layers):
+            self.egnn.graph_layers[0].reset_table_memos()       # (a change of first_layer_table: the next table forward builds)
         self._table_mode_seen = mode
         if mode == "off" or (mode == "auto" and not self.sigma_uniform_hint):
-            return False
-        if not layer.table_applies_to(layer._edge_chain_pack(), n_nodes, self.egnn.embedding_in.out_features, coord_dimension):
             return False
         n_classes = self.num_atom_types + 1
         n_even = kernels.egnn_table_points(coord_dimension)
         return not (mode == "auto" and n_classes ** 2 * (2 * n_even - 1) * 8 > n_edge_rows)
 
-    def _class_rows_serve_first_layer(self, n_nodes: int, coord_dimension: int) -> bool:
-        """With the table serving the first layer: may the forward leave h [n_nodes, H] and the first projections unmade
+    def _class_rows_serve_first_layer(self) -> bool:
+        """With the table serving the first layer: would the forward leave h [n_nodes, H] and the first projections unmade
         (first_layer_class_rows)?  Only under the sampler's uniform-sigma hint -- a direct forward keeps its per-node h."""
-        layers = self.egnn.graph_layers
-        if not (self.first_layer_class_rows and self.sigma_uniform_hint):
-            return False
-        following = layers[1] if len(layers) > 1 else None
-        return layers[0].class_rows_apply(layers[0]._edge_chain_pack(), n_nodes, self.egnn.embedding_in.out_features,
-                                          coord_dimension, following)
+        return self.first_layer_class_rows and self.sigma_uniform_hint
 
-    def _first_layer_table(self, edges, z, h, sigma, atom_types, k_vectors, second, serves=None):
-        """kernels.EgnnTable for the first graph layer when first_layer_table selects it and the layer's shape allows it, else
-        None.  The grid problem's per-node projections are mdx_egnn_node_inputs' second output for one node per class at
-        sigma[0]: the arithmetic of the batch's own first_proj.  serves: _table_serves_first_layer's answer when the caller
-        has asked already (h may then be None: only z is looked at)."""
+    def _first_layer_table(self, edges, z, h, sigma, atom_types, k_vectors, second, route=None):
+        """kernels.EgnnTable for the first graph layer when its route runs on the table, else None.  The grid problem's
+        per-node projections are mdx_egnn_node_inputs' second output for one node per class at sigma[0]: the arithmetic of the
+        batch's own first_proj.  route: the forward's first (h may then be None: only z is looked at); a caller without one
+        gets what first_layer_table and the layer's shape give."""
         from ... import kernels
-        if serves is None:
-            serves = self._table_serves_first_layer(edges.shape[0], z.shape[0], z.shape[1])
-        if not serves:
+        if route is None:
+            route = self._routes(z.shape[0], z.shape[1], edges.shape[0],
+                                 table=self._table_serves_first_layer(edges.shape[0], z.shape[1]))[0]
+        if route.path.edge != "table":
             return None
         layer = self.egnn.graph_layers[0]
         n_classes = self.num_atom_types + 1
@@ -272,7 +270,7 @@ class EGNNScoreNetwork(ScoreNetwork):
         emb = self.egnn.embedding_in
         # the memo's stamp: the inputs of the grid's node projections (the layer adds its own pack) -- a change resets the key
         stamp = kernels.parameter_stamp(emb.weight, emb.bias, *second)
-        memo = layer.table_memo(layer._edge_chain_pack(), n_classes, n_even, emb.out_features, z.shape[1], z.device, stamp)
+        memo = layer.table_memo(route.edge_pack, n_classes, n_even, emb.out_features, z.shape[1], z.device, stamp)
         if not self.first_layer_table_reuse:
             memo.reset()
         _, _, grid_proj = kernels.egnn_node_inputs(grid_x, k_vectors.contiguous(), sigma, classes.reshape(1, G),
@@ -303,7 +301,9 @@ class EGNNScoreNetwork(ScoreNetwork):
             gamma[:, 2 * k + 1, 2 * k] = k_vectors[k]
         return gamma
 
-    def _build_edges(self, relative_coordinates: torch.Tensor, lattice_parameters: torch.Tensor):
+    def _build_edges(self, relative_coordinates: torch.Tensor, lattice_parameters: torch.Tensor, routes=None):
+        """(edges, degree) of the batch's graph.  routes: the forward's, when it has made them for the capacity-sized list
+        (_static_edge_list_fits reads them)."""
         bsz, n, d = relative_coordinates.shape
         if self.edges == "fully_connected":
             # (the list depends on the batch's shape alone: built once per shape and device, reused by every forward -- and by
@@ -327,7 +327,7 @@ class EGNNScoreNetwork(ScoreNetwork):
         if self.graph_status is None or self.graph_status.device != relative_coordinates.device:
             self.graph_status = torch.zeros(1, dtype=torch.int32, device=relative_coordinates.device)
         capacity = bsz * n * (n - 1)
-        if relative_coordinates.is_cuda and not torch.is_grad_enabled() and self._static_edge_list_fits(bsz, n, relative_coordinates.device):
+        if relative_coordinates.is_cuda and not torch.is_grad_enabled() and self._static_edge_list_fits(bsz, n, relative_coordinates.device, routes):
             # clip, diagonal cell, cartesian positions, hit masks and emission behind one call (two launches)
             edges, degree, offsets, n_edges = neighbors.get_edges_static_clipped(
                 relative_coordinates, lattice_parameters.to(torch.float32), 2.2 * self.radial_cutoff, self.radial_cutoff,
@@ -337,18 +337,22 @@ class EGNNScoreNetwork(ScoreNetwork):
         return neighbors.get_edges_with_radial_cutoff(relative_coordinates, torch.diag_embed(lengths), self.radial_cutoff,
                                                       status=self.graph_status, return_degree=True)
 
-    def _static_edge_list_fits(self, bsz: int, n: int, device) -> bool:
+    def _static_edge_list_fits(self, bsz: int, n: int, device, routes=None) -> bool:
         """May the radius graph of a [bsz, n] batch go into a capacity-sized list (no host read per forward)?  Every graph
         layer must run the fused edge chain (nothing else then needs the edge count on the host) and the list must cost less
         than `static_edge_list_max_fraction` of the device's free memory; the answer is kept per shape (hipMemGetInfo is not
-        allowed while a stream is capturing: the eager warm-up iterations that precede every capture ask first)."""
+        allowed while a stream is capturing: the eager warm-up iterations that precede every capture ask first).
+        routes: those of a forward on the capacity-sized list, when the caller has them; else they are asked for here."""
         capacity = bsz * n * (n - 1)
         if self.spatial_dimension != 3:      # (1-D / 2-D radius graphs go through the padded two-call search: utils/neighbors.py)
             return False
-        if capacity <= 0 or not all(layer.use_fused_ops and layer._edge_chain_pack() is not None
-                                    for layer in self.egnn.graph_layers):
+        if capacity <= 0:
             return False
-        width = max((layer._edge_chain_pack().hidden for layer in self.egnn.graph_layers), default=0)
+        if routes is None:
+            routes = self._routes(bsz * n, 2 * self.bloch_wave_reciprocal_lattice_vectors.shape[0], capacity)
+        if not all(route.edge_pack is not None for route in routes):
+            return False
+        width = max((route.edge_pack.hidden for route in routes), default=0)
         needed = capacity * 20 + (capacity // 16 + bsz * n) * width * 4
         key = (str(device), capacity, width, self.static_edge_list_max_fraction)
         decisions = self.__dict__.setdefault("_static_decisions", {})
@@ -387,51 +391,68 @@ class EGNNScoreNetwork(ScoreNetwork):
             self.graph_status = torch.zeros(1, dtype=torch.int32, device=x.device)
         for layer in self.egnn.graph_layers:       # where the fused edge chain reports MDX_STATUS_EGNN_F16_RANGE
             layer.status_word = self.graph_status if x.is_cuda else None
-        edges, degree = self._build_edges(x, comp.L)
-
         emb = self.egnn.embedding_in
         sigma_in = batch[NOISE]
-        if (x.is_cuda and not torch.is_grad_enabled() and d == 3 and x.dtype == torch.float32 and
-                emb.in_features == self.num_atom_types + 2 and sigma_in.numel() == bsz):
-            # inputs and outputs around the EGNN as one launch each (mdx_egnn_node_inputs / mdx_egnn_scores) instead of
-            # ~25 elementwise passes per forward; the same arithmetic (see include/mdx_hip.h)
+        # inputs and outputs around the EGNN as one launch each (mdx_egnn_node_inputs / mdx_egnn_scores) instead of ~25
+        # elementwise passes per forward; the same arithmetic (see include/mdx_hip.h)
+        fused = (x.is_cuda and not torch.is_grad_enabled() and d == 3 and x.dtype == torch.float32 and
+                 emb.in_features == self.num_atom_types + 2 and sigma_in.numel() == bsz)
+        head = self.egnn.node_classification_layer
+        # (classification layer with the MASK logit at -inf, scores and the zero lattice output as one launch)
+        one_launch_head = head.out_features <= 8 and head.in_features % 4 == 0 and comp.L.dtype == torch.float32
+        coord_dimension = 2 * self.bloch_wave_reciprocal_lattice_vectors.shape[0]
+
+        def forward_routes(n_edge_rows):
+            """What every graph layer will run, settled from shapes and attributes BEFORE the per-node inputs: on the table,
+            inside a sampler, the first needs neither h nor its projections per node (first_layer_class_rows); the last, when
+            nobody reads the logits, no node path."""
+            return self._routes(bsz * n, coord_dimension, n_edge_rows,
+                                table=self._table_serves_first_layer(n_edge_rows, coord_dimension),
+                                class_rows=self._class_rows_serve_first_layer(),
+                                coords_only=one_launch_head and self.skip_unread_logits and self.logits_unread_hint)
+
+        # a radius graph goes into a capacity-sized list when every route has an edge chain (and the list fits): the routes
+        # are then made once, for that list, before the graph
+        capacity = bsz * n * (n - 1)
+        routes = forward_routes(capacity) if fused and self.edges == "radial_cutoff" and self.edge_builder is None and \
+            capacity > 0 else None
+        edges, degree = self._build_edges(x, comp.L, routes)
+        if fused:
             from ... import kernels
             k_vectors = self.bloch_wave_reciprocal_lattice_vectors.to(x)
-            second = self._first_projection_of_inputs()
-            # what the first graph layer will run on is settled from shapes and attributes, BEFORE the per-node inputs: on the
-            # table, inside a sampler, it needs neither h nor its projections per node (first_layer_class_rows)
-            coord_dimension = 2 * k_vectors.shape[0]
-            serves = second is not None and self._table_serves_first_layer(edges.shape[0], bsz * n, coord_dimension)
-            class_rows = serves and self._class_rows_serve_first_layer(bsz * n, coord_dimension)
-            res = kernels.egnn_node_inputs(x.contiguous(), k_vectors.contiguous(),
-                                           sigma_in.to(device=x.device, dtype=torch.float32).reshape(-1).contiguous(),
-                                           comp.A.reshape(bsz, n).long().contiguous(), emb.weight.detach().contiguous(),
-                                           emb.bias.detach().contiguous(), second=None if class_rows else second,
-                                           with_h=not class_rows)
-            z, h, first_proj = res if len(res) == 3 else (res[0], res[1], None)
-            table = self._first_layer_table(edges, z, h, sigma_in, comp.A, k_vectors, second, serves=True) if serves else None
-            row_class = None
+            if routes is None or edges.shape[0] != capacity:
+                routes = forward_routes(edges.shape[0])
+            first = routes[0] if routes else None
+            second = self._first_projection_of_inputs(first.edge_pack) if first is not None else None
+            class_rows = first is not None and first.path.class_rows
+            inputs = kernels.egnn_node_inputs(x.contiguous(), k_vectors.contiguous(),
+                                              sigma_in.to(device=x.device, dtype=torch.float32).reshape(-1).contiguous(),
+                                              comp.A.reshape(bsz, n).long().contiguous(), emb.weight.detach().contiguous(),
+                                              emb.bias.detach().contiguous(), second=None if class_rows else second,
+                                              with_h=not class_rows)
+            z, h = inputs[:2]
+            first_proj = inputs[2] if second is not None and not class_rows else None
+            table = row_class = None
+            if first is not None and first.path.edge == "table":
+                table = self._first_layer_table(edges, z, h, sigma_in, comp.A, k_vectors, second, route=first)
             if class_rows:
                 h, row_class = table.memo.grid_h[:table.n_classes], table.atom_types
-            head = self.egnn.node_classification_layer
-            if head.out_features <= 8 and head.in_features % 4 == 0 and comp.L.dtype == torch.float32:
-                # classification layer (MASK logit at -inf), scores and the zero lattice output: one launch
-                out = self.egnn(h=h, edges=edges, x=z, degree=degree, embedded=True, first_proj=first_proj, classify=False,
-                                first_table=table, coords_only=self.skip_unread_logits and self.logits_unread_hint,
-                                first_row_class=row_class)
-                if out.A is None:
-                    scores = kernels.egnn_scores(z, out.X.contiguous(), k_vectors.contiguous())
-                    return AXL(A=None, X=scores.reshape(bsz, n, d), L=torch.zeros_like(comp.L))
+            out = self.egnn(h, edges, z, degree, routes=routes, first_proj=first_proj, first_table=table,
+                            first_row_class=row_class)
+            h, x_hat = out.A, out.X                           # (A: the last layer's h)
+            if routes and routes[-1].path.coords_only:         # (h is None)
+                scores = kernels.egnn_scores(z, x_hat.contiguous(), k_vectors.contiguous())
+                return AXL(A=None, X=scores.reshape(bsz, n, d), L=torch.zeros_like(comp.L))
+            if one_launch_head:
                 scores, logits, zeros = kernels.egnn_outputs(
-                    z, out.X.contiguous(), k_vectors.contiguous(), out.A.contiguous(), head.weight.detach().contiguous(),
+                    z, x_hat.contiguous(), k_vectors.contiguous(), h.contiguous(), head.weight.detach().contiguous(),
                     head.bias.detach().contiguous(), self.num_atom_types, comp.L.numel())
                 logits = logits.reshape(bsz, n, -1)
                 logits._mdx_mask_imposed = True
                 return AXL(A=logits, X=scores.reshape(bsz, n, d), L=zeros.reshape(comp.L.shape))
-            out = self.egnn(h=h, edges=edges, x=z, degree=degree, embedded=True, first_proj=first_proj, first_table=table,
-                            first_row_class=row_class)
-            scores = kernels.egnn_scores(z, out.X.contiguous(), k_vectors.contiguous())
-            return AXL(A=out.A.reshape(bsz, n, -1), X=scores.reshape(bsz, n, d), L=torch.zeros_like(comp.L))
+            logits = head(h)
+            scores = kernels.egnn_scores(z, x_hat.contiguous(), k_vectors.contiguous())
+            return AXL(A=logits.reshape(bsz, n, -1), X=scores.reshape(bsz, n, d), L=torch.zeros_like(comp.L))
 
         flat = x.reshape(bsz * n, d)
         k_vectors = self.bloch_wave_reciprocal_lattice_vectors.to(flat)

@@ -1121,7 +1121,7 @@ def test_node_mlp_rows_against_fp64(cuda, precision, H, n_inner, M, with_residua
 # ---------------------------------------------------------------------------------------------------------------------
 def _unequal_width_net(cuda, precision="f16x3"):
     """message / coordinate width 64, node width 32: h and the messages differ in width, so the node MLP takes the
-    Linear(2H -> H) library GEMM + kernels.RowChainPack path (models/egnn.py::_forward_edge_chain) and not NodeMlpPack."""
+    Linear(2H -> H) library GEMM + kernels.RowChainPack path (models/egnn.py::E_GCL.run) and not NodeMlpPack."""
     from diffusion_for_multi_scale_molecular_dynamics_amd.models.score_networks.egnn_score_network import (
         EGNNScoreNetwork, EGNNScoreNetworkParameters)
     torch.manual_seed(23)
