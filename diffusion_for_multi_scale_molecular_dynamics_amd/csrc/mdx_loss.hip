@@ -17,7 +17,10 @@
 // OR-ed atomically, as everywhere in this library.  64-wide wavefronts are assumed (gfx950).
 //
 // The consistency regularizer's target and loss (mdx_consistency_loss) are the second member of the family, further down; the
-// regression regularizer's target and error (mdx_regression_loss) the third.
+// regression regularizer's target and error (mdx_regression_loss) the third.  The fourth, mdx_denoising_loss_gradient, is
+// denoising_loss_kernel<true>: the same body, which also writes d loss / d predicted_x, d loss / d logits and
+// d loss / d predicted_l (the closed form is in include/mdx_hip.h) and the structures' binary64 aggregates, which
+// structure_total_kernel adds in structure order for the batch's loss.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -58,6 +61,20 @@ struct LossArgs {
     uint32_t* status;
 };
 
+// what mdx_denoising_loss_gradient makes beside the forward's outputs: d loss / d prediction of
+// loss = sum_b (lambda_x mean_x[b] + lambda_l mean_l[b] + lambda_a mean_a[b]) / batch_divisor, and the structures' aggregates
+struct GradientOutputs {
+    double batch_divisor;
+    float *gradient_x, *gradient_a, *gradient_l;
+    double* structure_sums;
+};
+
+// the kernel's argument: the forward instantiation takes LossArgs alone, as before
+template <bool kGradient>
+struct KernelArgs : LossArgs {};
+template <>
+struct KernelArgs<true> : LossArgs, GradientOutputs {};
+
 // torch.clip(min=floor): a NaN stays a NaN
 __device__ __forceinline__ double clip_min(double v, double floor_value) { return v < floor_value ? floor_value : v; }
 
@@ -73,12 +90,23 @@ __device__ __forceinline__ double squared_error(double predicted, double target,
     return algorithm == MDX_LOSS_WEIGHTED_MSE ? mse * (exp(exponent * (sigma - sigma0)) + 1.0) : mse;
 }
 
+// d squared_error / d predicted
+__device__ __forceinline__ double squared_error_gradient(double predicted, double target, int algorithm, double sigma,
+                                                         double sigma0, double exponent)
+{
+    const double slope = 2.0 * (predicted - target);
+    return algorithm == MDX_LOSS_WEIGHTED_MSE ? slope * (exp(exponent * (sigma - sigma0)) + 1.0) : slope;
+}
+
 __device__ __forceinline__ void store(float* out, int64_t i, double v)
 {
     if (out) out[i] = (float)v;
 }
 
-__global__ __launch_bounds__(kBlock) void denoising_loss_kernel(const LossArgs a)
+// kGradient: the same body also writes the derivative of the batch's loss with respect to the three predictions
+// (mdx_denoising_loss_gradient); every line of it stands under `if constexpr`, so the forward instantiation is the code it was
+template <bool kGradient>
+__global__ __launch_bounds__(kBlock) void denoising_loss_kernel(const KernelArgs<kGradient> a)
 {
     __shared__ double tables[3][kMaxClasses * kMaxClasses];      // Q_t, Qbar_t, Qbar_{t-1} of this structure
     __shared__ double partial[2][kMaxWaves];
@@ -132,6 +160,11 @@ __global__ __launch_bounds__(kBlock) void denoising_loss_kernel(const LossArgs a
             store(a.target_x, i, target);
             store(a.loss_x, i, loss);
             sum_x += loss;
+            if constexpr (kGradient) {
+                const double scale = a.lambda_x / (a.batch_divisor * (double)ND);
+                store(a.gradient_x, i,
+                      scale * squared_error_gradient((double)a.predicted_x[i], target, a.x_algorithm, s, a.x_sigma0, a.x_exponent));
+            }
         }
     }
 
@@ -153,6 +186,7 @@ __global__ __launch_bounds__(kBlock) void denoising_loss_kernel(const LossArgs a
                     store(a.vb_term, out + c, nan);
                     store(a.ce_term, out + c, nan);
                     store(a.loss_a, out + c, nan);
+                    if constexpr (kGradient) store(a.gradient_a, out + c, nan);
                 }
                 sum_a += nan;
                 continue;
@@ -160,6 +194,12 @@ __global__ __launch_bounds__(kBlock) void denoising_loss_kernel(const LossArgs a
             double probability[kMaxClasses], cross_entropy[kMaxClasses], variational[kMaxClasses];
 #pragma unroll
             for (int c = 0; c < kMaxClasses; ++c) probability[c] = cross_entropy[c] = variational[c] = 0.0;
+            // the gradient's own registers: the softmax before the clip, and d vb / d p_j (then d vb / d softmax_k)
+            double softmax[kGradient ? kMaxClasses : 1], slope[kGradient ? kMaxClasses : 1], clipped_total = 1.0;
+            if constexpr (kGradient) {
+#pragma unroll
+                for (int c = 0; c < kMaxClasses; ++c) softmax[c] = slope[c] = 0.0;
+            }
             if (a.logits) {
                 // softmax and log_softmax with the largest logit taken out; probabilities clipped at eps and renormalised
                 // (utils/d3pm_utils.py:127-150); -log_softmax with the MASK column forced to 0, kept at a_0 (:41-46 of the calculator)
@@ -185,6 +225,7 @@ __global__ __launch_bounds__(kBlock) void denoising_loss_kernel(const LossArgs a
                     if (c < C) {
                         const double raw = probability[c] / total;
                         raw_sum += raw;
+                        if constexpr (kGradient) softmax[c] = raw;
                         probability[c] = clip_min(raw, a.eps);
                         clipped_sum += probability[c];
                         const double nll = c == C - 1 ? 0.0 : -((logit[c] - largest) - log_total);
@@ -195,7 +236,9 @@ __global__ __launch_bounds__(kBlock) void denoising_loss_kernel(const LossArgs a
 #pragma unroll
                 for (int c = 0; c < kMaxClasses; ++c)
                     if (c < C) probability[c] = probability[c] / clipped_sum;
+                if constexpr (kGradient) clipped_total = clipped_sum;
             }
+            double p_denominator_of_atom = 1.0;
             if (with_tables) {
                 // P(a_{t-1} = i | a_t, gamma) = (gamma Qbar_{t-1})_i (Q_t)_{i, a_t} / (gamma Qbar_t)_{a_t}  (utils/d3pm_utils.py:105-124)
                 // for gamma = the one-hot a_0 (a one-hot row times a matrix is that row: every other term is an exact zero) and for
@@ -206,6 +249,7 @@ __global__ __launch_bounds__(kBlock) void denoising_loss_kernel(const LossArgs a
 #pragma unroll
                     for (int j = 0; j < kMaxClasses; ++j)
                         if (j < C) p_denominator += probability[j] * Qbar[j * C + ct];
+                    if constexpr (kGradient) p_denominator_of_atom = p_denominator;
                 }
 #pragma unroll
                 for (int i = 0; i < kMaxClasses; ++i) {
@@ -224,6 +268,16 @@ __global__ __launch_bounds__(kBlock) void denoising_loss_kernel(const LossArgs a
                             // (loss/atom_type_loss_calculator.py:113-124)
                             const double log_p = log(clip_min(p_posterior, a.eps));
                             variational[i] = time_index == 0 ? -log_p * (i == c0 ? 1.0 : 0.0) : xlogx(q_posterior) - q_posterior * log_p;
+                            if constexpr (kGradient) {
+                                // d vb / d pi_i = -q_i / pi_i, at time index 0 -delta(i, a_0) / pi_i; torch's clamp passes the
+                                // gradient where pi_i >= eps and gives 0 elsewhere (a select: no 0 x inf).  Then through
+                                // pi_i = step_i (sum_j p_j Qbar_tm1[j, i]) / Dn and Dn = sum_j p_j Qbar[j, a_t] to p_j, x Dn
+                                const double kept = time_index == 0 ? (i == c0 ? 1.0 : 0.0) : q_posterior;
+                                const double to_posterior = p_posterior >= a.eps ? -kept / p_posterior : 0.0;
+#pragma unroll
+                                for (int j = 0; j < kMaxClasses; ++j)
+                                    if (j < C) slope[j] += to_posterior * (step * Qbar_tm1[j * C + i] - p_posterior * Qbar[j * C + ct]);
+                            }
                         }
                     }
                 }
@@ -243,6 +297,37 @@ __global__ __launch_bounds__(kBlock) void denoising_loss_kernel(const LossArgs a
                     }
                 }
                 sum_a += atom_sum;
+                if constexpr (kGradient) {
+                    if (with_tables && a.gradient_a) {
+                        // p = u / sum(u), u = max(softmax, eps) (the clip passes where softmax_k >= eps), then the softmax
+                        double through_sum = 0.0, through_softmax = 0.0;
+#pragma unroll
+                        for (int j = 0; j < kMaxClasses; ++j) {
+                            if (j < C) {
+                                slope[j] = slope[j] / p_denominator_of_atom;
+                                through_sum += slope[j] * probability[j];
+                            }
+                        }
+#pragma unroll
+                        for (int k = 0; k < kMaxClasses; ++k) {
+                            if (k < C) {
+                                const double to_clipped = (slope[k] - through_sum) / clipped_total;
+                                slope[k] = softmax[k] >= a.eps ? to_clipped : 0.0;
+                                through_softmax += softmax[k] * slope[k];
+                            }
+                        }
+                        // the cross-entropy: ce_weight (softmax_c - delta(c, a_0)) unless a_0 is MASK, whose term is forced to 0
+                        const double scale = a.lambda_a / (a.batch_divisor * (double)(N * C));
+                        const double ce_weight = c0 == C - 1 ? 0.0 : a.ce_weight;
+#pragma unroll
+                        for (int c = 0; c < kMaxClasses; ++c) {
+                            if (c < C) {
+                                const double to_logit = softmax[c] * (slope[c] - through_softmax);
+                                a.gradient_a[out + c] = (float)(scale * (to_logit + ce_weight * (softmax[c] - (c == c0 ? 1.0 : 0.0))));
+                            }
+                        }
+                    }
+                }
             }
         }
     }
@@ -259,6 +344,11 @@ __global__ __launch_bounds__(kBlock) void denoising_loss_kernel(const LossArgs a
         store(a.target_l, i, target);
         store(a.loss_l, i, loss);
         lattice[tid] = loss;
+        if constexpr (kGradient) {
+            const double scale = a.lambda_l / (a.batch_divisor * (double)P);
+            store(a.gradient_l, i,
+                  scale * squared_error_gradient((double)a.predicted_l[i], target, a.l_algorithm, s, a.l_sigma0, a.l_exponent));
+        }
     }
 
     // ---- means: lanes by the butterfly, wavefronts and lattice parameters in order
@@ -269,7 +359,9 @@ __global__ __launch_bounds__(kBlock) void denoising_loss_kernel(const LossArgs a
         partial[1][wave] = sum_a;
     }
     __syncthreads();
-    if (tid == 0 && a.per_structure) {
+    bool with_means = tid == 0 && a.per_structure;
+    if constexpr (kGradient) with_means = tid == 0 && (a.per_structure || a.structure_sums);
+    if (with_means) {
         double total_x = 0.0, total_a = 0.0, total_l = 0.0;
         for (int w = 0; w < waves; ++w) {
             total_x += partial[0][w];
@@ -282,11 +374,16 @@ __global__ __launch_bounds__(kBlock) void denoising_loss_kernel(const LossArgs a
         const double mean_l = a.predicted_l ? total_l / (double)P : 0.0;
         // the reference's order (models/axl_diffusion_lightning_model.py:325-338): X, then L, then A
         const double aggregate = (a.lambda_x * mean_x + a.lambda_l * mean_l) + a.lambda_a * mean_a;
-        float* row = a.per_structure + b * 4;
-        row[0] = (float)mean_a;
-        row[1] = (float)mean_x;
-        row[2] = (float)mean_l;
-        row[3] = (float)aggregate;
+        if (a.per_structure) {
+            float* row = a.per_structure + b * 4;
+            row[0] = (float)mean_a;
+            row[1] = (float)mean_x;
+            row[2] = (float)mean_l;
+            row[3] = (float)aggregate;
+        }
+        if constexpr (kGradient) {
+            if (a.structure_sums) a.structure_sums[b] = aggregate;
+        }
     }
     if (bits && a.status) atomicOr(a.status, bits);
 }
@@ -439,21 +536,19 @@ __global__ __launch_bounds__(kBlock) void regression_loss_kernel(const Regressio
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-int mdx_denoising_loss(const float* x0, const float* xt, const float* target_x_in, const float* predicted_x, const float* sigma,
-                       int sigma_per_element, const int64_t* a0, const int64_t* at, const float* logits,
-                       const int64_t* time_indices, const float* q_matrices, const float* q_bar_matrices,
-                       const float* q_bar_tm1_matrices, int total_time_steps, const float* l0, const float* lt,
-                       const float* predicted_l, const float* sigma_n, float sigma_n_divisor, int64_t batch, int number_of_atoms,
-                       int spatial_dimension,
-                       int num_classes, int number_of_lattice_parameters, int kmax, int x_algorithm, double x_sigma0,
-                       double x_exponent, int l_algorithm, double l_sigma0, double l_exponent, double ce_weight, double eps,
-                       double lambda_a, double lambda_x, double lambda_l, float* target_x, float* target_l, float* loss_x,
-                       float* loss_a, float* loss_l, float* per_structure, float* q_atm1, float* p_atm1, float* vb_term,
-                       float* ce_term, uint32_t* status, mdx_stream_t stream)
+// mdx_denoising_loss (gradient == nullptr: the forward instantiation) and mdx_denoising_loss_gradient (gradient given, `loss`
+// nullable): the checks of both, then the one launch, then the family's one-workgroup total for `loss`
+int denoising_loss_entry(const float* x0, const float* xt, const float* target_x_in, const float* predicted_x, const float* sigma,
+                         int sigma_per_element, const int64_t* a0, const int64_t* at, const float* logits,
+                         const int64_t* time_indices, const float* q_matrices, const float* q_bar_matrices,
+                         const float* q_bar_tm1_matrices, int total_time_steps, const float* l0, const float* lt,
+                         const float* predicted_l, const float* sigma_n, float sigma_n_divisor, int64_t batch, int number_of_atoms,
+                         int spatial_dimension, int num_classes, int number_of_lattice_parameters, int kmax, int x_algorithm,
+                         double x_sigma0, double x_exponent, int l_algorithm, double l_sigma0, double l_exponent, double ce_weight,
+                         double eps, double lambda_a, double lambda_x, double lambda_l, float* target_x, float* target_l,
+                         float* loss_x, float* loss_a, float* loss_l, float* per_structure, float* q_atm1, float* p_atm1,
+                         float* vb_term, float* ce_term, uint32_t* status, mdx_stream_t stream, const GradientOutputs* gradient,
+                         float* loss)
 {
     const int N = number_of_atoms, D = spatial_dimension, C = num_classes, P = number_of_lattice_parameters;
     const bool with_x = predicted_x != nullptr, with_a = a0 != nullptr, with_l = predicted_l != nullptr;
@@ -485,8 +580,16 @@ int mdx_denoising_loss(const float* x0, const float* xt, const float* target_x_i
     } else if (target_l || loss_l) {
         return MDX_ERR_INVALID_ARG;
     }
+    if (gradient) {
+        // a part that is absent has no gradient; the atom types' needs the whole chain, logits and tables
+        if (!(gradient->batch_divisor > 0.0)) return MDX_ERR_INVALID_ARG;
+        if (gradient->gradient_x && !with_x) return MDX_ERR_INVALID_ARG;
+        if (gradient->gradient_a && !(with_a && logits && any_table)) return MDX_ERR_INVALID_ARG;
+        if (gradient->gradient_l && !with_l) return MDX_ERR_INVALID_ARG;
+        if (loss && !gradient->structure_sums) return MDX_ERR_INVALID_ARG;
+    }
     if (batch == 0) return MDX_OK;
-    LossArgs a;
+    KernelArgs<true> a;
     a.x0 = x0, a.xt = xt, a.target_x_in = target_x_in, a.predicted_x = predicted_x, a.sigma = sigma;
     a.sigma_per_element = sigma_per_element ? 1 : 0;
     a.a0 = a0, a.at = at, a.logits = logits, a.time_indices = time_indices;
@@ -501,8 +604,65 @@ int mdx_denoising_loss(const float* x0, const float* xt, const float* target_x_i
     a.status = status;
     int64_t threads = cdiv((int64_t)N * D, kWave) * kWave;
     threads = threads > kBlock ? kBlock : threads;
-    hipLaunchKernelGGL(denoising_loss_kernel, dim3((unsigned)batch), dim3((unsigned)threads), 0, as_stream(stream), a);
+    if (gradient) {
+        static_cast<GradientOutputs&>(a) = *gradient;
+        hipLaunchKernelGGL(denoising_loss_kernel<true>, dim3((unsigned)batch), dim3((unsigned)threads), 0, as_stream(stream), a);
+        if (loss)
+            hipLaunchKernelGGL(structure_total_kernel, dim3(1), dim3(kBlock), 0, as_stream(stream), gradient->structure_sums,
+                               batch, gradient->batch_divisor, loss);
+    } else {
+        KernelArgs<false> forward;
+        static_cast<LossArgs&>(forward) = a;
+        hipLaunchKernelGGL(denoising_loss_kernel<false>, dim3((unsigned)batch), dim3((unsigned)threads), 0, as_stream(stream),
+                           forward);
+    }
     return launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+int mdx_denoising_loss(const float* x0, const float* xt, const float* target_x_in, const float* predicted_x, const float* sigma,
+                       int sigma_per_element, const int64_t* a0, const int64_t* at, const float* logits,
+                       const int64_t* time_indices, const float* q_matrices, const float* q_bar_matrices,
+                       const float* q_bar_tm1_matrices, int total_time_steps, const float* l0, const float* lt,
+                       const float* predicted_l, const float* sigma_n, float sigma_n_divisor, int64_t batch, int number_of_atoms,
+                       int spatial_dimension,
+                       int num_classes, int number_of_lattice_parameters, int kmax, int x_algorithm, double x_sigma0,
+                       double x_exponent, int l_algorithm, double l_sigma0, double l_exponent, double ce_weight, double eps,
+                       double lambda_a, double lambda_x, double lambda_l, float* target_x, float* target_l, float* loss_x,
+                       float* loss_a, float* loss_l, float* per_structure, float* q_atm1, float* p_atm1, float* vb_term,
+                       float* ce_term, uint32_t* status, mdx_stream_t stream)
+{
+    return denoising_loss_entry(x0, xt, target_x_in, predicted_x, sigma, sigma_per_element, a0, at, logits, time_indices, q_matrices,
+                                q_bar_matrices, q_bar_tm1_matrices, total_time_steps, l0, lt, predicted_l, sigma_n, sigma_n_divisor,
+                                batch, number_of_atoms, spatial_dimension, num_classes, number_of_lattice_parameters, kmax,
+                                x_algorithm, x_sigma0, x_exponent, l_algorithm, l_sigma0, l_exponent, ce_weight, eps, lambda_a,
+                                lambda_x, lambda_l, target_x, target_l, loss_x, loss_a, loss_l, per_structure, q_atm1, p_atm1,
+                                vb_term, ce_term, status, stream, nullptr, nullptr);
+}
+
+int mdx_denoising_loss_gradient(const float* x0, const float* xt, const float* target_x_in, const float* predicted_x,
+                                const float* sigma, int sigma_per_element, const int64_t* a0, const int64_t* at,
+                                const float* logits, const int64_t* time_indices, const float* q_matrices,
+                                const float* q_bar_matrices, const float* q_bar_tm1_matrices, int total_time_steps,
+                                const float* l0, const float* lt, const float* predicted_l, const float* sigma_n,
+                                float sigma_n_divisor, int64_t batch, int number_of_atoms, int spatial_dimension, int num_classes,
+                                int number_of_lattice_parameters, int kmax, int x_algorithm, double x_sigma0, double x_exponent,
+                                int l_algorithm, double l_sigma0, double l_exponent, double ce_weight, double eps, double lambda_a,
+                                double lambda_x, double lambda_l, float* target_x, float* target_l, float* loss_x, float* loss_a,
+                                float* loss_l, float* per_structure, float* q_atm1, float* p_atm1, float* vb_term, float* ce_term,
+                                double batch_divisor, float* gradient_x, float* gradient_a, float* gradient_l,
+                                double* structure_sums, float* loss, uint32_t* status, mdx_stream_t stream)
+{
+    const GradientOutputs gradient = {batch_divisor, gradient_x, gradient_a, gradient_l, structure_sums};
+    return denoising_loss_entry(x0, xt, target_x_in, predicted_x, sigma, sigma_per_element, a0, at, logits, time_indices, q_matrices,
+                                q_bar_matrices, q_bar_tm1_matrices, total_time_steps, l0, lt, predicted_l, sigma_n, sigma_n_divisor,
+                                batch, number_of_atoms, spatial_dimension, num_classes, number_of_lattice_parameters, kmax,
+                                x_algorithm, x_sigma0, x_exponent, l_algorithm, l_sigma0, l_exponent, ce_weight, eps, lambda_a,
+                                lambda_x, lambda_l, target_x, target_l, loss_x, loss_a, loss_l, per_structure, q_atm1, p_atm1,
+                                vb_term, ce_term, status, stream, &gradient, loss);
 }
 
 int mdx_consistency_loss(const float* x_start, const float* x_end, const float* score, const float* sigma_start,

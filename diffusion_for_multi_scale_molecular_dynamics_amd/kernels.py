@@ -5,6 +5,7 @@ and contiguity of each against the header's parameter, appends torch's current H
 and returns torch tensors that PyTorch owns.  Nothing here computes on the CPU.
 """
 import ctypes as C
+import inspect
 from collections import namedtuple
 from dataclasses import dataclass
 from functools import lru_cache
@@ -744,6 +745,18 @@ def denoising_loss(*, x0=None, xt=None, target_x=None, predicted_x=None, sigma=N
     lambda_weights is (A, X, L).  Returns a DenoisingLoss of f32 tensors, None where its part is absent: the two targets, the
     three unreduced losses, per_structure [B, 4] = (mean A, mean X, mean L, weighted aggregate), and with `with_terms` the
     atom-type intermediates q_atm1, p_atm1, vb_term, ce_term [B, N, C]."""
+    return _denoising_loss_launch(x0, xt, target_x, predicted_x, sigma, a0, at, logits, time_indices, q_matrices, q_bar_matrices,
+                                  q_bar_tm1_matrices, tables_per_structure, l0, lt, predicted_l, sigma_n, sigma_n_divisor, kmax,
+                                  x_algorithm, x_sigma0, x_exponent, l_algorithm, l_sigma0, l_exponent, ce_weight, eps,
+                                  lambda_weights, with_terms, status)
+
+
+def _denoising_loss_launch(x0, xt, target_x, predicted_x, sigma, a0, at, logits, time_indices, q_matrices, q_bar_matrices,
+                           q_bar_tm1_matrices, tables_per_structure, l0, lt, predicted_l, sigma_n, sigma_n_divisor, kmax,
+                           x_algorithm, x_sigma0, x_exponent, l_algorithm, l_sigma0, l_exponent, ce_weight, eps, lambda_weights,
+                           with_terms, status, with_gradient: bool = False, batch_divisor: Optional[float] = None):
+    """The checks and the one call behind denoising_loss (mdx_denoising_loss) and, `with_gradient`,
+    denoising_loss_and_gradient (mdx_denoising_loss_gradient)."""
     _device_only("the denoising loss", x0=x0, xt=xt, target_x=target_x, predicted_x=predicted_x, sigma=sigma, a0=a0, at=at,
                  logits=logits, time_indices=time_indices, q_matrices=q_matrices, q_bar_matrices=q_bar_matrices,
                  q_bar_tm1_matrices=q_bar_tm1_matrices, l0=l0, lt=lt, predicted_l=predicted_l, sigma_n=sigma_n, status=status)
@@ -811,12 +824,68 @@ def denoising_loss(*, x0=None, xt=None, target_x=None, predicted_x=None, sigma=N
         q_atm1=empty(with_terms and with_tables, B, N, Cn), p_atm1=empty(with_terms and with_tables and with_logits, B, N, Cn),
         vb_term=empty(with_terms and with_tables and with_logits, B, N, Cn), ce_term=empty(with_terms and with_logits, B, N, Cn))
     lambda_a, lambda_x, lambda_l = (float(w) for w in lambda_weights)
-    call("mdx_denoising_loss", x0, xt, target_x, predicted_x, sigma, per_element, a0, at, logits, time_indices, q_matrices,
-         q_bar_matrices, q_bar_tm1_matrices, int(T), l0, lt, predicted_l, sigma_n, float(sigma_n_divisor), B, int(N), int(D), int(Cn), int(P), int(kmax),
-         LOSS_ALGORITHMS[x_algorithm], float(x_sigma0), float(x_exponent), LOSS_ALGORITHMS[l_algorithm], float(l_sigma0),
-         float(l_exponent), float(ce_weight), float(eps), lambda_a, lambda_x, lambda_l, out.target_x, out.target_l, out.loss_x,
-         out.loss_a, out.loss_l, out.per_structure, out.q_atm1, out.p_atm1, out.vb_term, out.ce_term, status)
-    return out
+    detached = [None if t is None else t.detach() for t in (predicted_x, logits, predicted_l)] if with_gradient else \
+        [predicted_x, logits, predicted_l]
+    arguments = (x0, xt, target_x, detached[0], sigma, per_element, a0, at, detached[1], time_indices, q_matrices,
+                 q_bar_matrices, q_bar_tm1_matrices, int(T), l0, lt, detached[2], sigma_n, float(sigma_n_divisor), B, int(N), int(D),
+                 int(Cn), int(P), int(kmax), LOSS_ALGORITHMS[x_algorithm], float(x_sigma0), float(x_exponent),
+                 LOSS_ALGORITHMS[l_algorithm], float(l_sigma0), float(l_exponent), float(ce_weight), float(eps), lambda_a, lambda_x,
+                 lambda_l, out.target_x, out.target_l, out.loss_x, out.loss_a, out.loss_l, out.per_structure, out.q_atm1, out.p_atm1,
+                 out.vb_term, out.ce_term)
+    if not with_gradient:
+        call("mdx_denoising_loss", *arguments, status)
+        return out
+    if B < 1:
+        raise ValueError("the gradient of the denoising loss of an empty batch is not defined")
+    divisor = float(B if batch_divisor is None else batch_divisor)
+    if not divisor > 0.0:
+        raise ValueError(f"batch_divisor must be positive, got {batch_divisor}")
+    gradient_x, gradient_l = empty(with_x, B, N, D), empty(with_l, B, P)
+    gradient_a = empty(with_tables and with_logits, B, N, Cn)
+    sums, loss = torch.empty(B, dtype=torch.float64, device=dev), torch.empty(1, dtype=F32, device=dev)
+    call("mdx_denoising_loss_gradient", *arguments, divisor, gradient_x, gradient_a, gradient_l, sums, loss, status)
+    loss = loss[0]
+    if any(t is not None and t.requires_grad for t in (predicted_x, logits, predicted_l)):
+        loss = _DenoisingLossFunction.apply(loss, predicted_x, logits, predicted_l, gradient_x, gradient_a, gradient_l)
+    return DenoisingLossGradient(*out, gradient_x=gradient_x, gradient_a=gradient_a, gradient_l=gradient_l, loss=loss)
+
+
+DenoisingLossGradient = namedtuple("DenoisingLossGradient", DenoisingLoss._fields + ("gradient_x", "gradient_a", "gradient_l", "loss"))
+
+
+class _DenoisingLossFunction(torch.autograd.Function):
+    """loss(predicted_x, logits, predicted_l) of mdx_denoising_loss_gradient for predictions that require grad: backward is
+    grad_output x the kernel's own gradient buffers, no second launch.  A prediction that is absent, or that the loss does not
+    depend on (logits without the tables), has no buffer and gets None."""
+
+    @staticmethod
+    def forward(ctx, loss, predicted_x, logits, predicted_l, gradient_x, gradient_a, gradient_l):
+        ctx.save_for_backward(gradient_x, gradient_a, gradient_l)
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        asked = ctx.needs_input_grad[1:4]
+        return (None, *(grad_output * buffer if wanted and buffer is not None else None
+                        for wanted, buffer in zip(asked, ctx.saved_tensors)), None, None, None)
+
+
+def denoising_loss_and_gradient(*, batch_divisor: Optional[float] = None, **arguments) -> DenoisingLossGradient:
+    """The denoising loss AND its gradient in one launch (mdx_denoising_loss_gradient, the family's one-workgroup total
+    after it), no host read.  Takes the keyword arguments of `denoising_loss`, and `batch_divisor` (default: B).  Returns a
+    DenoisingLossGradient: the fields of DenoisingLoss with the same bits, then
+      gradient_x [B, N, D], gradient_a [B, N, C], gradient_l [B, P]   d loss / d predicted_x, logits, predicted_l (None where
+                                                                       the part is absent; gradient_a needs logits and tables)
+      loss (0-dim f32) = sum_b (lambda_x mean_x[b] + lambda_l mean_l[b] + lambda_a mean_a[b]) / batch_divisor, added in binary64
+    When a prediction requires grad, loss carries it: its backward returns grad_output x the buffer for every prediction that
+    asked, without a second launch."""
+    unknown = sorted(set(arguments) - set(_DENOISING_LOSS_DEFAULTS))
+    if unknown:
+        raise TypeError(f"denoising_loss_and_gradient() got unexpected keyword arguments {unknown}")
+    return _denoising_loss_launch(**{**_DENOISING_LOSS_DEFAULTS, **arguments}, with_gradient=True, batch_divisor=batch_divisor)
+
+
+_DENOISING_LOSS_DEFAULTS = {name: parameter.default for name, parameter in inspect.signature(denoising_loss).parameters.items()}
 
 
 ConsistencyLoss = namedtuple("ConsistencyLoss", ["target", "gradient", "per_structure", "loss"])

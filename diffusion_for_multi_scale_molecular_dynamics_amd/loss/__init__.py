@@ -1,6 +1,7 @@
 """The loss calculators' factory (src/.../loss/__init__.py:7-41) and `denoising_loss`, the loss of a score network on a noised
 batch: what the reference's AXLDiffusionLightningModel._generic_step (models/axl_diffusion_lightning_model.py:186-381) returns
-for a test or validation batch, made by ONE launch of the fused loss kernel after the network's forward."""
+for a test or validation batch, made by ONE launch of the fused loss kernel after the network's forward; and `training_loss`,
+what its training_step optimises: the same with the gradient from the same launch, plus the weighted regularizer loss."""
 from typing import Any, Dict, Optional
 
 import torch
@@ -55,7 +56,7 @@ def _status_word(device: torch.device) -> torch.Tensor:
 
 
 def denoising_loss(axl_network, noised_batch: Dict[str, Any], loss_parameters: Optional[AXL] = None, kmax_target_score: int = 4,
-                   conditional: Optional[bool] = None) -> dict:
+                   conditional: Optional[bool] = None, differentiable: bool = False) -> dict:
     """The denoising loss of `axl_network` on a batch NoisingTransform noised (device tensors only).
 
     Returns _generic_step's dictionary: `unreduced_loss` (AXL of [B, N, C], [B, N, D], [B, P]), `loss` (0-dim), `sigmas`
@@ -64,7 +65,18 @@ def denoising_loss(axl_network, noised_batch: Dict[str, Any], loss_parameters: O
     `per_structure_loss` [B], the weighted aggregate of every structure (`loss` is its mean), and `status`, the device word
     the kernel reports the reference's value assertions into: nothing here reads it; kernels.raise_loss_status(status) does.
     The weights are the three lambda_weight of `loss_parameters` (default: create_loss_parameters({})).  `conditional` goes to
-    the network's forward as it is."""
+    the network's forward as it is.
+
+    `differentiable`: the predictions are not detached before the loss, the launch is mdx_denoising_loss_gradient (the same
+    kernel body, writing d loss / d prediction beside the loss) and `loss` is its binary64 total over the batch divided by B,
+    with a grad_fn whose backward hands the three gradient buffers to the network's autograd graph -- the loss the reference's
+    training_step optimises.  `model_predictions` and `unreduced_loss` stay detached, as in the reference (:343-352);
+    `prediction_gradients` (AXL) holds the kernel's three buffers, d loss / d prediction."""
+    return _denoising_step(axl_network, noised_batch, loss_parameters, kmax_target_score, conditional, differentiable)[0]
+
+
+def _denoising_step(axl_network, noised_batch, loss_parameters, kmax_target_score, conditional, differentiable):
+    """denoising_loss's dictionary, and the augmented batch the network saw (what a regularizer is given)."""
     parameters = create_loss_parameters({}) if loss_parameters is None else loss_parameters
     a0, x0, l0 = noised_batch[ATOM_TYPES], noised_batch[RELATIVE_COORDINATES], noised_batch[LATTICE_PARAMETERS]
     at, xt, lt = noised_batch[NOISY_ATOM_TYPES], noised_batch[NOISY_RELATIVE_COORDINATES], noised_batch[NOISY_LATTICE_PARAMETERS]
@@ -78,27 +90,45 @@ def denoising_loss(axl_network, noised_batch: Dict[str, Any], loss_parameters: O
     forces = noised_batch[CARTESIAN_FORCES] if CARTESIAN_FORCES in noised_batch else torch.zeros_like(x0)
     augmented_batch = {NOISY_AXL_COMPOSITION: noisy_composition, TIME: noised_batch[TIME], NOISE: noise, CARTESIAN_FORCES: forces}
     predictions = axl_network(augmented_batch, conditional=conditional)
+    attached = predictions
     predictions = AXL(A=predictions.A.detach(), X=predictions.X.detach(), L=predictions.L.detach())
     status = _status_word(x0.device)
     # sigma_n = sigma / N^(1/P) inside the kernel: the reference scales by the number of lattice parameters here
     # (models/axl_diffusion_lightning_model.py:275-277), not by the spatial dimension
-    out = kernels.denoising_loss(
-        x0=x0.contiguous(), xt=xt.contiguous(), predicted_x=predictions.X.contiguous(), sigma=noise.reshape(B).contiguous(),
-        a0=a0.contiguous(), at=at.contiguous(), logits=predictions.A.contiguous(), time_indices=time_indices.contiguous(),
+    launch, given = (kernels.denoising_loss_and_gradient, attached) if differentiable else (kernels.denoising_loss, predictions)
+    out = launch(
+        x0=x0.contiguous(), xt=xt.contiguous(), predicted_x=given.X.contiguous(), sigma=noise.reshape(B).contiguous(),
+        a0=a0.contiguous(), at=at.contiguous(), logits=given.A.contiguous(), time_indices=time_indices.contiguous(),
         q_matrices=_per_structure_rows(tables[0]), q_bar_matrices=_per_structure_rows(tables[1]),
         q_bar_tm1_matrices=_per_structure_rows(tables[2]), tables_per_structure=True,
-        l0=l0.contiguous(), lt=lt.contiguous(), predicted_l=predictions.L.contiguous(),
+        l0=l0.contiguous(), lt=lt.contiguous(), predicted_l=given.L.contiguous(),
         sigma_n_divisor=kernels.root_of_atom_count(N, l0.shape[-1]), kmax=kmax_target_score,
         **_weighted_scalars("x_", parameters.X), **_weighted_scalars("l_", parameters.L), ce_weight=parameters.A.ce_weight,
         eps=parameters.A.eps, lambda_weights=(parameters.A.lambda_weight, parameters.X.lambda_weight, parameters.L.lambda_weight),
         status=status)
     per_structure_loss = out.per_structure[:, 3]
     output = dict(unreduced_loss=AXL(A=out.loss_a, X=out.loss_x, L=out.loss_l),
-                  loss=per_structure_loss.mean(dtype=torch.float64).to(torch.float32),
+                  loss=out.loss if differentiable else per_structure_loss.mean(dtype=torch.float64).to(torch.float32),
                   sigmas=noise.reshape(B, 1, 1).expand(B, N, D), model_predictions=predictions,
                   target_coordinates_normalized_conditional_scores=out.target_x,
                   target_lattice_normalized_conditional_scores=out.target_l, per_structure_loss=per_structure_loss, status=status)
+    if differentiable:
+        output["prediction_gradients"] = AXL(A=out.gradient_a, X=out.gradient_x, L=out.gradient_l)
     output[AXL_COMPOSITION] = composition
     output[NOISY_AXL_COMPOSITION] = noisy_composition
     output[TIME] = augmented_batch[TIME]
+    return output, augmented_batch
+
+
+def training_loss(axl_network, noised_batch: Dict[str, Any], loss_parameters: Optional[AXL] = None, regularizer=None,
+                  current_epoch: int = 0, kmax_target_score: int = 4, conditional: Optional[bool] = None) -> dict:
+    """The loss the reference's training_step optimises (models/axl_diffusion_lightning_model.py:363-375, :447): the
+    differentiable denoising_loss, and -- with a `regularizer` whose can_regularizer_run() holds -- its weighted loss on the
+    same augmented batch added to `loss` and kept under `regularizer_loss`.  `loss.backward()` runs through both."""
+    output, augmented_batch = _denoising_step(axl_network, noised_batch, loss_parameters, kmax_target_score, conditional, True)
+    if regularizer and regularizer.can_regularizer_run():
+        weighted_regularizer_loss = regularizer.compute_weighted_regularizer_loss(
+            score_network=axl_network, augmented_batch=augmented_batch, current_epoch=current_epoch)
+        output["loss"] = output["loss"] + weighted_regularizer_loss
+        output["regularizer_loss"] = weighted_regularizer_loss
     return output

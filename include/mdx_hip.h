@@ -637,6 +637,46 @@ MDX_API int mdx_denoising_loss(const float* x0, const float* xt, const float* ta
                                float* per_structure, float* q_atm1, float* p_atm1, float* vb_term, float* ce_term,
                                uint32_t* status, mdx_stream_t stream);
 
+/* The denoising loss with its gradient (csrc/mdx_loss.hip; the same kernel body as mdx_denoising_loss, instantiated with the
+ * derivative switched on): every argument of mdx_denoising_loss up to ce_term in the same order and meaning, six more, then
+ * status and stream last as everywhere in this library.  It makes everything mdx_denoising_loss makes (the same bits), and in
+ * the same launch, one workgroup per structure, the derivative of
+ *   loss = (1 / batch_divisor) sum_b (lambda_x mean_x[b] + lambda_l mean_l[b] + lambda_a mean_a[b])
+ * with respect to predicted_x, logits and predicted_l; batch_divisor > 0 (the batch size for the mean over the batch).
+ *   gradient_x f32 [batch, N, D] = lambda_x 2 (s - t) w / (batch_divisor N D), w = 1 for MDX_LOSS_MSE and
+ *      exp(x_exponent (sigma - x_sigma0)) + 1 for MDX_LOSS_WEIGHTED_MSE; t is the binary64 target, not its rounded output
+ *   gradient_l f32 [batch, P]: the same with P for N D, l_algorithm, l_sigma0, l_exponent and the structure's sigma (not sigma_n)
+ *   gradient_a f32 [batch, N, C]: per atom, with r the softmax, u = max(r, eps), S = sum(u), p = u / S, step_i = Q[i, a_t],
+ *      Dn = sum_j p_j Qbar[j, a_t], pi_i = step_i sum_j p_j Qbar_tm1[j, i] / Dn (the forward's p(a_{t-1} | a_t)):
+ *        g_i = -q_i / pi_i, at time index 0 -delta(i, a_0) / pi_i, and 0 where pi_i < eps
+ *        h_j = sum_i g_i (step_i Qbar_tm1[j, i] - pi_i Qbar[j, a_t]) / Dn
+ *        v_k = (h_k - sum_j h_j p_j) / S where r_k >= eps, else 0
+ *        d / d z_c = r_c (v_c - sum_k r_k v_k) + ce_weight (r_c - delta(c, a_0))   (the second term 0 when a_0 is MASK)
+ *      times lambda_a / (batch_divisor N C).  The two clips pass the gradient where their argument is >= eps, equality
+ *      included, as torch.clamp does; they are selects, so a logit of -inf (r = 0) has an exact 0 and no 0 x inf arises.
+ *      xlogy(q, q) has no gradient.  gradient_a needs logits and the tables.
+ *   structure_sums f64 [batch]: the unrounded aggregates per_structure[:, 3] rounds; the caller's scratch, needed with loss
+ *   loss f32 [1] = (sum_b structure_sums[b]) / batch_divisor, added in structure order by the family's one-workgroup launch
+ * Each of the five outputs is nullable on its own; a gradient whose part is absent (its prediction NULL; for gradient_a also
+ * without tables) must be NULL, else MDX_ERR_INVALID_ARG.  Where the forward's rules give NaN -- an invalid sigma or
+ * coordinate, a time index or atom type outside its range, a softmax that does not sum to one -- the gradient's elements are
+ * NaN too and the same status bits are raised; the other structures keep their bits.  Binary64 from the promoted binary32
+ * inputs, every value rounded once, no atomics in the arithmetic, every sum in a fixed order, no host read: the same bits on
+ * every launch and hipGraph replay. */
+MDX_API int mdx_denoising_loss_gradient(const float* x0, const float* xt, const float* target_x_in, const float* predicted_x,
+                                        const float* sigma, int sigma_per_element, const int64_t* a0, const int64_t* at,
+                                        const float* logits, const int64_t* time_indices, const float* q_matrices,
+                                        const float* q_bar_matrices, const float* q_bar_tm1_matrices, int total_time_steps,
+                                        const float* l0, const float* lt, const float* predicted_l, const float* sigma_n,
+                                        float sigma_n_divisor, int64_t batch, int number_of_atoms, int spatial_dimension,
+                                        int num_classes, int number_of_lattice_parameters, int kmax, int x_algorithm,
+                                        double x_sigma0, double x_exponent, int l_algorithm, double l_sigma0, double l_exponent,
+                                        double ce_weight, double eps, double lambda_a, double lambda_x, double lambda_l,
+                                        float* target_x, float* target_l, float* loss_x, float* loss_a, float* loss_l,
+                                        float* per_structure, float* q_atm1, float* p_atm1, float* vb_term, float* ce_term,
+                                        double batch_divisor, float* gradient_x, float* gradient_a, float* gradient_l,
+                                        double* structure_sums, float* loss, uint32_t* status, mdx_stream_t stream);
+
 /* The consistency regularizer's target and loss (regularizers/consistency_regularizer.py:190-308, after Daras et al.;
  * csrc/mdx_loss.hip): for a batch of structures x_start f32 [batch, N, D] at noise sigma_start that the sampler carried to
  * x_end f32 [batch, N, D] at noise sigma_end < sigma_start, and the network's sigma-normalised score s f32 [batch, N, D] at the

@@ -1,0 +1,25 @@
+"""The denoising-gradient fixtures are what tests/golden/make_golden_denoising_gradient.py makes from the reference today
+(container-only), byte for byte, as tests/test_golden_denoising_loss_reproducible.py checks the denoising-loss ones.
+Skipped where the reference is absent."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+from conftest import GOLDEN, ROOT
+from denoising_gradient_cases import FILES
+from test_golden_reproducible import REFERENCE
+
+
+@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="the reference is not on this machine")
+def test_denoising_gradient_fixtures_reproduce(tmp_path):
+    env = dict(os.environ, PYTHONPATH=REFERENCE, MDX_GOLDEN_OUT=str(tmp_path))
+    run = subprocess.run([sys.executable, os.path.join(GOLDEN, "make_golden_denoising_gradient.py")], env=env, cwd=ROOT,
+                         capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0, run.stderr[-3000:]
+    assert os.listdir(tmp_path) == ["denoising_gradient"] and sorted(os.listdir(tmp_path / "denoising_gradient")) == sorted(FILES)
+    assert sorted(os.listdir(os.path.join(GOLDEN, "denoising_gradient"))) == sorted(FILES)
+    for name in FILES:
+        assert (tmp_path / "denoising_gradient" / name).read_bytes() == \
+            open(os.path.join(GOLDEN, "denoising_gradient", name), "rb").read(), name
