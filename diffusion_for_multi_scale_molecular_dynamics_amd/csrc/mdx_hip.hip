@@ -2232,6 +2232,7 @@ const char* mdx_status_string(int status)
         case MDX_STATUS_ANALYTICAL_SIGMA: return "All values of sigma should be larger than zero.";
         case MDX_STATUS_ANALYTICAL_COORDINATES: return "the relative coordinates should all be in [0, 1)";
         case MDX_STATUS_KS_NAN: return "a sample of the Kolmogorov-Smirnov metric holds a NaN";
+        case MDX_STATUS_OPTIMIZER_NONFINITE: return "a gradient of the optimizer step is not finite";
         default: return "unknown status";
     }
 }

@@ -1023,6 +1023,156 @@ def regression_loss(score=None, *, target=None, relative_coordinates=None, sigma
 
 
 # ----------------------------------------------------------------------------------------------------------------
+# the optimizer step: multi-tensor Adam / AdamW and the gradients' global norm (csrc/mdx_optimizer.hip)
+# ----------------------------------------------------------------------------------------------------------------
+ADAM_CHUNK_ELEMENTS = _hip.ADAM_CHUNK_ELEMENTS       # elements per workgroup: the granule of the per-block table
+ADAM_HYPER_NAMES = ("lr", "beta1", "beta2", "eps", "weight_decay", "max_norm", "gradient_scale")    # mdx_adam_hyper_fill's order
+
+
+def adam_chunk_table(counts) -> tuple:
+    """(block_tensor, block_offset): per workgroup the tensor it serves and its element offset in it, for tensors of `counts`
+    elements each -- ceil(count / ADAM_CHUNK_ELEMENTS) workgroups per tensor, in table order.  Host lists; no device."""
+    block_tensor, block_offset = [], []
+    for k, count in enumerate(counts):
+        if count < 1:
+            raise ValueError(f"tensor {k} of the table has {count} elements: a tensor without elements is left out of it")
+        for offset in range(0, count, ADAM_CHUNK_ELEMENTS):
+            block_tensor.append(k)
+            block_offset.append(offset)
+    return block_tensor, block_offset
+
+
+def adam_counter_slots(counts) -> tuple:
+    """(slots, total): the entry of the step-counter array of each tensor's first chunk, for tensors of `counts` elements laid
+    out one after another -- one entry per chunk of ADAM_CHUNK_ELEMENTS elements, none for a tensor without elements -- and
+    the number of entries."""
+    slots, total = [], 0
+    for count in counts:
+        slots.append(total)
+        total += -(-int(count) // ADAM_CHUNK_ELEMENTS)
+    return slots, total
+
+
+def _adam_upload(values, dtype, device) -> torch.Tensor:
+    """A host list as a device table (the one host-to-device copy of a plan: tests count its calls)."""
+    return torch.tensor(values, dtype=dtype, device=device)
+
+
+@dataclass
+class AdamPlan:
+    """The device tables of one parameter group for mdx_adam_step / mdx_gradient_norm, and the norm's workspace."""
+
+    key: tuple
+    addresses: Optional[torch.Tensor]      # int64 [tensors, 4]: p, g, exp_avg, exp_avg_sq
+    counts: Optional[torch.Tensor]         # int64 [tensors]
+    slots: Optional[torch.Tensor]          # int32 [tensors]: the entry of the step counters of each tensor's first chunk
+    block_tensor: Optional[torch.Tensor]   # int32 [blocks]
+    block_offset: Optional[torch.Tensor]   # int64 [blocks]
+    number_of_blocks: int
+    partials: Optional[torch.Tensor]       # f64 [blocks]
+    norm: Optional[torch.Tensor]           # f64 [2]: the norm and its square
+    device: Optional[torch.device]
+    counters: int = 0                      # the step-counter entries the plan reaches: 1 + the highest
+
+
+_ADAM_PLANS = {}
+_ADAM_PLANS_KEPT = 64
+
+
+def adam_plan(parameters, gradients=None, exp_avg=None, exp_avg_sq=None, slots=None, names=None) -> AdamPlan:
+    """The tables of a parameter group, built once per tuple of (data pointers, count, slot) and cached under it: parameters
+    with their gradients (default: each parameter's .grad), first and second moments, and the entry of the step-counter array
+    of each one's first chunk (default: adam_counter_slots of the parameters' sizes: one entry per chunk, in order).  Refused before anything is uploaded or launched: a host tensor (MdxError), a dtype other
+    than float32 or a non-contiguous tensor (ValueError naming it), moments or gradients of another size.  A tensor without
+    elements is skipped: it takes no row of the tables."""
+    parameters = list(parameters)
+    count = len(parameters)
+    gradients = [p.grad for p in parameters] if gradients is None else list(gradients)
+    names = [f"parameters[{i}]" for i in range(count)] if names is None else list(names)
+    slots = adam_counter_slots([p.numel() for p in parameters])[0] if slots is None else [int(s) for s in slots]
+    if exp_avg is None or exp_avg_sq is None:
+        raise ValueError("adam_plan needs the first and second moments (exp_avg, exp_avg_sq) of every parameter")
+    exp_avg, exp_avg_sq = list(exp_avg), list(exp_avg_sq)
+    if not (len(gradients) == len(exp_avg) == len(exp_avg_sq) == len(names) == len(slots) == count):
+        raise ValueError("adam_plan: parameters, gradients, exp_avg, exp_avg_sq, slots and names must have one entry per parameter")
+    rows, sizes, kept_slots = [], [], []
+    for name, p, g, m, v, slot in zip(names, parameters, gradients, exp_avg, exp_avg_sq, slots):
+        group = {name: p, name + ".grad": g, name + ".exp_avg": m, name + ".exp_avg_sq": v}
+        if any(t is None for t in group.values()):
+            raise ValueError(f"{name}: a parameter without a gradient or moments is left out of the plan, not passed as None")
+        _device_only("the optimizer step", **group)
+        for label, t in group.items():
+            if t.dtype != F32:
+                raise ValueError(f"{label} has dtype {t.dtype}: the optimizer step serves float32 only")
+            if not t.is_contiguous():
+                raise ValueError(f"{label} is not contiguous: the optimizer step addresses each tensor as one flat array")
+            if t.numel() != p.numel():
+                raise ValueError(f"{label} has {t.numel()} elements, {name} has {p.numel()}")
+        if p.numel() == 0:
+            continue
+        rows.append((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()))
+        sizes.append(p.numel())
+        kept_slots.append(slot)
+    key = tuple(row + (size, slot) for row, size, slot in zip(rows, sizes, kept_slots))
+    plan = _ADAM_PLANS.get(key)
+    if plan is not None:
+        return plan
+    if not rows:
+        plan = AdamPlan(key, None, None, None, None, None, 0, None, None, None)
+    else:
+        device = next(p for p in parameters if p.numel()).device
+        block_tensor, block_offset = adam_chunk_table(sizes)
+        plan = AdamPlan(key, _adam_upload(rows, I64, device), _adam_upload(sizes, I64, device),
+                        _adam_upload(kept_slots, I32, device), _adam_upload(block_tensor, I32, device),
+                        _adam_upload(block_offset, I64, device), len(block_tensor),
+                        torch.empty(len(block_tensor), dtype=F64, device=device), torch.empty(2, dtype=F64, device=device), device,
+                        max(slot + -(-size // ADAM_CHUNK_ELEMENTS) for size, slot in zip(sizes, kept_slots)))
+    if len(_ADAM_PLANS) >= _ADAM_PLANS_KEPT:
+        _ADAM_PLANS.clear()
+    _ADAM_PLANS[key] = plan
+    return plan
+
+
+def adam_hyper_fill(hyper, lr, beta1, beta2, eps, weight_decay, max_norm, gradient_scale):
+    """Write the hyper-parameter buffer (f64 [ADAM_HYPER_COUNT], device) from host values: one tiny launch, no copy."""
+    _device_only("the optimizer step", hyper=hyper)
+    if hyper.numel() < _hip.ADAM_HYPER_COUNT:
+        raise ValueError(f"hyper holds {hyper.numel()} values, mdx_adam_hyper_fill writes {_hip.ADAM_HYPER_COUNT}")
+    call("mdx_adam_hyper_fill", float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), float(max_norm),
+         float(gradient_scale), hyper)
+
+
+def gradient_norm(plan: AdamPlan) -> Optional[torch.Tensor]:
+    """f64 [2] on the device: the 2-norm of all gradients of the plan and its square (mdx_gradient_norm: two launches, no host
+    read, a fixed summation order).  The plan's own buffer: the next call overwrites it.  None for a plan without tensors."""
+    if plan.number_of_blocks == 0:
+        return None
+    call("mdx_gradient_norm", plan.addresses, plan.counts, plan.block_tensor, plan.block_offset, plan.number_of_blocks,
+         plan.partials, plan.norm)
+    return plan.norm
+
+
+def adam_step(plan: AdamPlan, steps, hyper, decoupled_weight_decay: bool, zero_gradients: bool = False, clip: bool = False,
+              status: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """One Adam / AdamW step of every tensor of the plan in one launch (mdx_adam_step); with `clip`, gradient_norm first and
+    the gradients scaled by min(1, max_norm / (norm + 1e-6)) inside the step: .grad itself is not rewritten.  steps int32: the
+    counters, one entry per chunk at the plan's slots (adam_counter_slots); hyper f64 [ADAM_HYPER_COUNT] as adam_hyper_fill
+    writes it.  Returns the norm buffer when one was computed.  A gradient that is not finite sets STATUS_OPTIMIZER_NONFINITE in
+    `status` (int32 [1], optional)."""
+    if plan.number_of_blocks == 0:
+        return None
+    _device_only("the optimizer step", steps=steps, hyper=hyper, status=status)
+    if steps.numel() < plan.counters:
+        raise ValueError(f"the plan reaches {plan.counters} step counters; steps holds {steps.numel()}")
+    if hyper.numel() < _hip.ADAM_HYPER_COUNT:
+        raise ValueError(f"hyper holds {hyper.numel()} values, expected {_hip.ADAM_HYPER_COUNT}")
+    norm = gradient_norm(plan) if clip else None
+    call("mdx_adam_step", plan.addresses, plan.counts, plan.slots, plan.block_tensor, plan.block_offset, plan.number_of_blocks,
+         steps, hyper, norm, int(bool(decoupled_weight_decay)), int(bool(zero_gradients)), status)
+    return norm
+
+
+# ----------------------------------------------------------------------------------------------------------------
 # sampling metrics: sort and two-sample Kolmogorov-Smirnov rank (csrc/mdx_metrics.hip)
 # ----------------------------------------------------------------------------------------------------------------
 KS_MAX_SAMPLES = _hip.KS_MAX_SAMPLES     # per sample: every product of a count and a reduced size stays below 2^48

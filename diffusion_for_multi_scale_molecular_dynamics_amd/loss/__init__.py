@@ -1,7 +1,9 @@
 """The loss calculators' factory (src/.../loss/__init__.py:7-41) and `denoising_loss`, the loss of a score network on a noised
 batch: what the reference's AXLDiffusionLightningModel._generic_step (models/axl_diffusion_lightning_model.py:186-381) returns
 for a test or validation batch, made by ONE launch of the fused loss kernel after the network's forward; and `training_loss`,
-what its training_step optimises: the same with the gradient from the same launch, plus the weighted regularizer loss."""
+what its training_step optimises: the same with the gradient from the same launch, plus the weighted regularizer loss; and the
+driver around it, `configure_optimizers` and `optimisation_step`: what Lightning does around training_step with the reference's
+`optimizer:` / `scheduler:` blocks and the trainer's gradient_clipping and accumulate_grad_batches."""
 from typing import Any, Dict, Optional
 
 import torch
@@ -13,6 +15,8 @@ from ..namespace import (ATOM_TYPES, AXL, AXL_COMPOSITION, CARTESIAN_FORCES, LAT
 from .atom_type_loss_calculator import D3PMLossCalculator
 from .coordinates_loss_calculator import MSELossCalculator, WeightedMSELossCalculator
 from .loss_parameters import create_loss_parameters
+from ..models.optimizer import FusedAdam, create_optimizer_parameters, load_optimizer
+from ..models.scheduler import create_scheduler_parameters, load_scheduler_dictionary
 
 LOSS_BY_ALGO = dict(mse=MSELossCalculator, weighted_mse=WeightedMSELossCalculator)
 
@@ -131,4 +135,53 @@ def training_loss(axl_network, noised_batch: Dict[str, Any], loss_parameters: Op
             score_network=axl_network, augmented_batch=augmented_batch, current_epoch=current_epoch)
         output["loss"] = output["loss"] + weighted_regularizer_loss
         output["regularizer_loss"] = weighted_regularizer_loss
+    return output
+
+
+def configure_optimizers(hyper_params, axl_network) -> dict:
+    """dict(optimizer=..., [lr_scheduler=..., monitor=...]) as the reference's Lightning model returns it
+    (models/axl_diffusion_lightning_model.py:147-167).  `hyper_params`: an object with `optimizer_parameters` and
+    `scheduler_parameters` (the reference's AXLDiffusionParameters, also as a checkpoint's pickle gives them), or a configuration
+    dictionary with an `optimizer` block and, optionally, a `scheduler` block."""
+    if isinstance(hyper_params, dict):
+        optimizer_parameters = create_optimizer_parameters(dict(hyper_params["optimizer"]))
+        scheduler_parameters = create_scheduler_parameters(hyper_params)
+    else:
+        optimizer_parameters = hyper_params.optimizer_parameters
+        scheduler_parameters = getattr(hyper_params, "scheduler_parameters", None)
+    optimizer = load_optimizer(optimizer_parameters, axl_network)
+    output = dict(optimizer=optimizer)
+    if scheduler_parameters is not None:
+        output.update(load_scheduler_dictionary(scheduler_parameters=scheduler_parameters, optimizer=optimizer))
+    return output
+
+
+def optimisation_step(axl_network, noised_batch: Dict[str, Any], optimizer, loss_parameters: Optional[AXL] = None, regularizer=None,
+                      current_epoch: int = 0, batch_index: int = 0, gradient_clipping: float = 0.0,
+                      accumulate_grad_batches: int = 1, kmax_target_score: int = 4, conditional: Optional[bool] = None) -> dict:
+    """What Lightning does around the reference's training_step for one batch: training_loss, the backward of
+    loss / accumulate_grad_batches, and -- on every accumulate_grad_batches-th batch (by `batch_index`) -- the optimizer's step
+    with the gradients clipped at the global norm `gradient_clipping` (0: off, as in train_diffusion.py:192), then gradients of
+    zero.  Returns training_loss's dictionary, with `gradient_norm` (0-dim, device) when a norm was computed.
+
+    With a FusedAdam the step, the clipping and the zeroing are its launches (the clipped values are used, `.grad` is never
+    rewritten with them); any other optimizer gets torch's clip_grad_norm_, step() and zero_grad(set_to_none=False).  Nothing
+    is read from the device.  No epoch loop, data module, logging or checkpoint writing: those are the caller's."""
+    if accumulate_grad_batches < 1:
+        raise ValueError(f"accumulate_grad_batches is {accumulate_grad_batches}: it counts batches, so at least 1")
+    output = training_loss(axl_network, noised_batch, loss_parameters, regularizer, current_epoch, kmax_target_score, conditional)
+    (output["loss"] / accumulate_grad_batches).backward()
+    if (batch_index + 1) % accumulate_grad_batches != 0:
+        return output
+    if isinstance(optimizer, FusedAdam):
+        optimizer.gradient_clip_val, optimizer.zero_gradients = float(gradient_clipping), True
+        optimizer.step()
+        if optimizer.last_gradient_norm is not None:
+            output["gradient_norm"] = optimizer.last_gradient_norm[0].clone()
+    else:
+        if gradient_clipping > 0.0:
+            parameters = [p for group in optimizer.param_groups for p in group["params"]]
+            output["gradient_norm"] = torch.nn.utils.clip_grad_norm_(parameters, gradient_clipping)
+        optimizer.step()
+        optimizer.zero_grad(set_to_none=False)
     return output

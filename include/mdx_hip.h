@@ -78,6 +78,8 @@ extern "C" {
                                             structure's (atom's) atom-type results are NaN and no table entry is read       */
 #define MDX_STATUS_KS_NAN 262144u        /* mdx_sort_keys: a NaN among the values (scipy's nan_policy='propagate': the
                                             Kolmogorov-Smirnov distance of such a sample is NaN); the output is unspecified  */
+#define MDX_STATUS_OPTIMIZER_NONFINITE 524288u /* mdx_adam_step: a scaled, clipped gradient that is not finite; the arithmetic
+                                            goes on as torch's does (the NaN propagates into the parameter and its state)    */
 
 #define MDX_MAX_CLASSES 8      /* C supported by the fused atom-type kernels */
 #define MDX_PREDICTOR 0
@@ -758,6 +760,58 @@ MDX_API int mdx_sort_keys(const void* values, int64_t n, int values_are_f64, dou
 MDX_API int64_t mdx_ks_two_sample_workspace_bytes(int64_t n1, int64_t n2);
 MDX_API int mdx_ks_two_sample_sorted(const double* a_sorted, int64_t n1, const double* b_sorted, int64_t n2, void* workspace,
                                      int64_t* numerator_out, mdx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The optimizer step (csrc/mdx_optimizer.hip): torch's single-tensor Adam and AdamW (amsgrad off, maximize off) -- what the
+ * reference's load_optimizer constructs (models/optimizer.py:60-82) -- on every tensor of a parameter group in one launch, and
+ * the global 2-norm of the group's gradients that torch's clip_grad_norm_ (Lightning's gradient_clip_algorithm="norm") clips by.
+ *
+ * The tables describe the group; the host writes them once, they are device memory:
+ *   addresses uint64 [tensors, 4]   the addresses of p, g, exp_avg, exp_avg_sq: binary32, contiguous, 4-byte aligned
+ *   counts int64 [tensors]          the elements of each (> 0: a tensor without elements is left out)
+ *   counter_slots int32 [tensors]   (mdx_adam_step) the entry of `steps` of each tensor's first chunk: the counters outlive a table
+ *   block_tensor int32 [blocks], block_offset int64 [blocks]   per workgroup: the tensor it serves and its element offset in it;
+ *                                   a tensor of n elements is served by ceil(n / MDX_ADAM_CHUNK_ELEMENTS) workgroups at offsets
+ *                                   0, MDX_ADAM_CHUNK_ELEMENTS, ... in table order.  An offset outside [0, n) does nothing.
+ * A tensor without a gradient in some call is left out of that call's tables.
+ *
+ * mdx_adam_step, with t = the tensor's counter after this step and hyper f64 [MDX_ADAM_HYPER_COUNT] in device memory (a
+ * captured launch follows a scheduler's learning rate; mdx_adam_hyper_fill writes it from its arguments, a launch and no copy):
+ *   g  = (gradient_scale clip) grad          clip = 1 with norm == NULL, else min(1, max_norm / (norm[0] + 1e-6))
+ *   decoupled_weight_decay 0 (Adam):   g = g + weight_decay p;  q = p
+ *   decoupled_weight_decay 1 (AdamW):  q = p (1 - lr weight_decay)
+ *   m' = m + (g - m) (1 - beta1)
+ *   v' = beta2 v + (1 - beta2) g g
+ *   p' = q - (lr / (1 - beta1^t)) m' / (sqrt(v') / sqrt(1 - beta2^t) + eps)
+ * The four operands of an element are widened to binary64, the form above is evaluated in binary64 in this order without
+ * contraction, and each of p', m', v' is rounded to binary32 once.  steps int32 holds the steps taken, ONE ENTRY
+ * PER CHUNK: the workgroup at element offset o of tensor k owns entry counter_slots[k] + o / MDX_ADAM_CHUNK_ELEMENTS, reads it,
+ * uses t = entry + 1 and stores t.  All chunks of a tensor hold the same value (a call serves all of them or none), so every
+ * workgroup of a tensor uses the same t and none reads what another writes; a tensor's step is its first chunk's entry.
+ * With zero_gradients every consumed gradient is overwritten by +0.0.  16-byte accesses where a tensor's four addresses are 16-byte aligned, dwords otherwise: the same bits.
+ * A g that is not finite sets MDX_STATUS_OPTIMIZER_NONFINITE in status (nullable); the arithmetic goes on.
+ *
+ * mdx_gradient_norm: norm f64 [2] = the 2-norm of all gradients in the tables and its square.  Squares and sums in binary64, a
+ * fixed tree per chunk into partials f64 [blocks] (the caller's scratch), then one small launch adds them in a fixed tree.
+ * Two launches; with it and clipping a step is three.  No atomics in the arithmetic: the same bits on every launch and replay. */
+#define MDX_ADAM_CHUNK_ELEMENTS 2048
+#define MDX_ADAM_HYPER_LR 0
+#define MDX_ADAM_HYPER_BETA1 1
+#define MDX_ADAM_HYPER_BETA2 2
+#define MDX_ADAM_HYPER_EPS 3
+#define MDX_ADAM_HYPER_WEIGHT_DECAY 4
+#define MDX_ADAM_HYPER_MAX_NORM 5
+#define MDX_ADAM_HYPER_GRADIENT_SCALE 6
+#define MDX_ADAM_HYPER_COUNT 8
+MDX_API int mdx_adam_hyper_fill(double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm,
+                                double gradient_scale, double* hyper, mdx_stream_t stream);
+MDX_API int mdx_gradient_norm(const uint64_t* addresses, const int64_t* counts, const int32_t* block_tensor,
+                              const int64_t* block_offset, int64_t number_of_blocks, double* partials, double* norm,
+                              mdx_stream_t stream);
+MDX_API int mdx_adam_step(const uint64_t* addresses, const int64_t* counts, const int32_t* counter_slots,
+                          const int32_t* block_tensor, const int64_t* block_offset, int64_t number_of_blocks, int32_t* steps,
+                          const double* hyper, const double* norm, int decoupled_weight_decay, int zero_gradients,
+                          uint32_t* status, mdx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Fused score network: the reference's MLPScoreNetwork (models/score_networks/mlp_score_network.py:54-370,
