@@ -9,7 +9,7 @@ import inspect
 from collections import namedtuple
 from dataclasses import dataclass
 from functools import lru_cache
-from typing import Optional
+from typing import Any, Optional
 
 import torch
 
@@ -1434,7 +1434,198 @@ def mlp_forward(pack: MlpPack, atom_types, x, l, time, sigma):
     return logits, score_x, score_l
 
 
-NOISE_WORKSPACE_MAX_FLOATS = 1 << 28        # 1 GiB cap; longer segments are split into several launches by the library
+# ----------------------------------------------------------------------------------------------------------------
+# training the MLP score network: forward with an activation record, and the parameters' gradient (csrc/mdx_mlp_train.hip)
+# ----------------------------------------------------------------------------------------------------------------
+MLP_TRAIN_STRUCTURES_PER_SLAB = _hip.MLP_TRAIN_STRUCTURES_PER_SLAB     # structures one workgroup of the backward adds up
+
+
+def mlp_train_layers(network) -> list:
+    """[(name of the nn.Linear in the module, the nn.Linear)] of the unconditional forward, in the order of the address table
+    and of the flat gradient buffer: the order named_parameters() gives these parameters."""
+    names = ["relative_coordinates_embedding_layer", "noise_embedding_layer", "time_embedding_layer",
+             "atom_type_embedding_layer", "lattice_parameters_embedding_layer"]
+    layers = [(name, getattr(network, name)) for name in names]
+    layers += [(f"mlp_layers.{k}", layer) for k, layer in enumerate(network.mlp_layers)]
+    return layers + [(name, getattr(network, name)) for name in ("output_A_layer", "output_X_layer", "output_L_layer")]
+
+
+def mlp_train_refusal(network) -> Optional[str]:
+    """Why the training kernels do not cover this network, or None: they evaluate MLPScoreNetwork._single, nothing around it."""
+    if getattr(network, "use_permutation_invariance", False):
+        return "the fused MLP training kernels do not cover the permutation symmetrisation (use_permutation_invariance)"
+    if getattr(network, "use_time_dependent_prefactor", False):
+        return "the fused MLP training kernels do not cover the time-dependent prefactor (use_time_dependent_prefactor)"
+    if len(network.mlp_layers) > _hip.MLP_MAX_HIDDEN:
+        return f"the fused MLP training kernels serve at most {_hip.MLP_MAX_HIDDEN} hidden layers, the network has {len(network.mlp_layers)}"
+    if network.num_classes > _hip.MAX_CLASSES:
+        return f"the fused MLP training kernels serve at most {_hip.MAX_CLASSES} classes, the network has {network.num_classes}"
+    return None
+
+
+@dataclass
+class MlpTrainPlan:
+    """What mdx_mlp_train_forward / _backward need of one MLPScoreNetwork: the shape words, the device table of the parameters'
+    addresses and the parameters themselves in table order (weight, bias per layer)."""
+
+    key: tuple
+    shape: Any                           # int32 [MLP_TRAIN_SHAPE_COUNT], host (ctypes)
+    addresses: torch.Tensor              # int64 [2 layers], device
+    names: list                          # the parameters' names in the module, in table order
+    parameters: list
+    sizes: list
+    number_of_atoms: int
+    spatial_dimension: int
+    num_classes: int
+    lattice_parameters: int
+    record_floats: int
+    parameter_count: int
+    device: torch.device
+    workspace: Optional[torch.Tensor] = None      # f64, grown on demand: the slabs of the last backward
+
+    def workspace_doubles(self, batch: int) -> int:
+        return int(lib().mdx_mlp_train_workspace_doubles(self.shape, int(batch)))
+
+    def views(self, flat: torch.Tensor) -> list:
+        """The per-parameter views of a flat gradient buffer, in table order, each of its parameter's shape."""
+        return [piece.view(p.shape) for piece, p in zip(torch.split(flat, self.sizes), self.parameters)]
+
+
+_MLP_TRAIN_PLANS = {}
+_MLP_TRAIN_PLANS_KEPT = 16
+
+
+def mlp_train_plan(network) -> MlpTrainPlan:
+    """The plan of `network`, built once per tuple of (shape, data pointers) and cached under it -- the parameters are read in
+    place, so an optimizer step needs no new plan, and a parameter that moved gets one.  Refused before anything is uploaded:
+    a network the kernels do not cover (MdxError with the reason), a host parameter (MdxError), a parameter that is not float32
+    or not contiguous (ValueError naming it)."""
+    reason = mlp_train_refusal(network)
+    if reason:
+        raise _hip.MdxError(reason)
+    hp = network._hyper_params
+    words = (network._natoms, network.spatial_dimension, network.num_classes, hp.hidden_dimensions_size, len(network.mlp_layers),
+             hp.relative_coordinates_embedding_dimensions_size, hp.noise_embedding_dimensions_size,
+             hp.time_embedding_dimensions_size, hp.atom_type_embedding_dimensions_size,
+             hp.lattice_parameters_embedding_dimensions_size)
+    names, parameters = [], []
+    for name, layer in mlp_train_layers(network):
+        names += [name + ".weight", name + ".bias"]
+        parameters += [layer.weight, layer.bias]
+    _device_only("the MLP training step", **dict(zip(names, parameters)))
+    for name, p in zip(names, parameters):
+        if p.dtype != F32:
+            raise ValueError(f"{name} has dtype {p.dtype}: the MLP training kernels serve float32 only")
+        if not p.is_contiguous():
+            raise ValueError(f"{name} is not contiguous: the MLP training kernels read each parameter as one [out, in] array")
+    key = words + tuple(p.data_ptr() for p in parameters)
+    plan = _MLP_TRAIN_PLANS.get(key)
+    if plan is not None and all(held is p for held, p in zip(plan.parameters, parameters)):
+        return plan
+    shape = (C.c_int32 * _hip.MLP_TRAIN_SHAPE_COUNT)(*words)
+    record_floats, parameter_count = lib().mdx_mlp_train_record_floats(shape), lib().mdx_mlp_train_parameter_count(shape)
+    sizes = [p.numel() for p in parameters]
+    if record_floats < 0 or parameter_count != sum(sizes):
+        raise _hip.MdxError(f"the MLP training kernels do not serve the shape {words}: the library counts {parameter_count} "
+                            f"parameters, the module's layers hold {sum(sizes)}")
+    device = parameters[0].device
+    d = network.spatial_dimension
+    plan = MlpTrainPlan(key, shape, _adam_upload([p.data_ptr() for p in parameters], I64, device), names, parameters, sizes,
+                        network._natoms, d, network.num_classes, d * (d + 1) // 2, int(record_floats), int(parameter_count), device)
+    if len(_MLP_TRAIN_PLANS) >= _MLP_TRAIN_PLANS_KEPT:
+        _MLP_TRAIN_PLANS.clear()
+    _MLP_TRAIN_PLANS[key] = plan
+    return plan
+
+
+MlpTrainForward = namedtuple("MlpTrainForward", ["logits", "score_x", "score_l", "record"])
+MlpTrainGradients = namedtuple("MlpTrainGradients", ["flat", "views"])
+
+
+def mlp_train_forward(plan: MlpTrainPlan, atom_types, x, l, time, sigma) -> MlpTrainForward:
+    """MLPScoreNetwork._single in one launch, on the module's own parameters (mdx_mlp_train_forward): the RAW head outputs --
+    logits [B, N, C] without the -inf of the MASK class, score_x [B, N, d], score_l [B, nl] -- and the activation record
+    [B, plan.record_floats] that mlp_train_backward reads.  time, sigma: [B, 1] or [B]."""
+    _device_only("the MLP training forward", atom_types=atom_types, x=x, l=l, time=time, sigma=sigma)
+    if x.dim() != 3 or tuple(x.shape[1:]) != (plan.number_of_atoms, plan.spatial_dimension):
+        raise ValueError(f"x has shape {tuple(x.shape)}, expected [B, {plan.number_of_atoms}, {plan.spatial_dimension}]")
+    B = x.shape[0]
+    for name, t, shape in (("atom_types", atom_types, (B, plan.number_of_atoms)), ("l", l, (B, plan.lattice_parameters))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {shape}")
+    for name, t in (("time", time), ("sigma", sigma)):
+        if t.numel() != B:
+            raise ValueError(f"{name} has shape {tuple(t.shape)}: expected one value per structure, [{B}, 1]")
+    logits = torch.empty(B, plan.number_of_atoms, plan.num_classes, dtype=F32, device=x.device)
+    score_x = torch.empty(B, plan.number_of_atoms, plan.spatial_dimension, dtype=F32, device=x.device)
+    score_l = torch.empty(B, plan.lattice_parameters, dtype=F32, device=x.device)
+    record = torch.empty(B, plan.record_floats, dtype=F32, device=x.device)
+    call("mdx_mlp_train_forward", plan.shape, plan.addresses, atom_types, x, l, time, sigma, B, logits, score_x, score_l, record)
+    return MlpTrainForward(logits, score_x, score_l, record)
+
+
+def mlp_train_backward(plan: MlpTrainPlan, record, grad_logits, grad_x, grad_l, out=None, accumulate: bool = False,
+                       scale: float = 1.0, workspace=None) -> MlpTrainGradients:
+    """The gradient of every parameter of the plan from a forward's record and the cotangents of its three outputs, each of
+    which may be None (mdx_mlp_train_backward: two launches, a fixed summation order, each element rounded to binary32 once).
+    out: the flat float32 buffer [plan.parameter_count] in table order (default: a fresh one); `accumulate` adds its old value
+    before the rounding, `scale` multiplies the sum (1 / accumulate_grad_batches).  workspace: f64, at least
+    plan.workspace_doubles(B) (default: the plan's own, grown on demand).  Returns (flat, its per-parameter views)."""
+    _device_only("the MLP training backward", record=record, grad_logits=grad_logits, grad_x=grad_x, grad_l=grad_l, out=out,
+                 workspace=workspace)
+    if record.dim() != 2 or record.shape[1] != plan.record_floats:
+        raise ValueError(f"record has shape {tuple(record.shape)}, expected [B, {plan.record_floats}]")
+    B = record.shape[0]
+    expected = (("grad_logits", grad_logits, (B, plan.number_of_atoms, plan.num_classes)),
+                ("grad_x", grad_x, (B, plan.number_of_atoms, plan.spatial_dimension)), ("grad_l", grad_l, (B, plan.lattice_parameters)))
+    for name, t, shape in expected:
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {shape}")
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate adds to the buffer's old value: it needs `out`")
+        out = torch.empty(plan.parameter_count, dtype=F32, device=record.device)
+    elif out.dim() != 1 or out.numel() != plan.parameter_count:
+        raise ValueError(f"out has shape {tuple(out.shape)}, expected [{plan.parameter_count}]")
+    needed = plan.workspace_doubles(B)
+    if workspace is None:
+        if plan.workspace is None or plan.workspace.numel() < needed:
+            plan.workspace = torch.empty(max(needed, 1), dtype=F64, device=record.device)
+        workspace = plan.workspace
+    elif workspace.numel() < needed:
+        raise ValueError(f"workspace holds {workspace.numel()} doubles, a batch of {B} needs {needed}")
+    call("mdx_mlp_train_backward", plan.shape, plan.addresses, record, grad_logits, grad_x, grad_l, B, workspace,
+         int(bool(accumulate)), float(scale), out)
+    return MlpTrainGradients(out, plan.views(out))
+
+
+class _MlpTrainFunction(torch.autograd.Function):
+    """(logits, score_x, score_l) of mdx_mlp_train_forward as a function of the plan's parameters: backward is
+    mdx_mlp_train_backward into a fresh flat buffer, whose per-parameter views autograd accumulates into .grad."""
+
+    @staticmethod
+    def forward(ctx, plan, atom_types, x, l, time, sigma, *parameters):
+        out = mlp_train_forward(plan, atom_types, x, l, time, sigma)
+        ctx.plan = plan
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(out.record, *parameters)       # the parameters: autograd refuses a backward after they changed
+        return out.logits, out.score_x, out.score_l
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_logits, grad_x, grad_l):
+        record = ctx.saved_tensors[0]
+        given = [None if g is None else g.contiguous() for g in (grad_logits, grad_x, grad_l)]
+        gradients = mlp_train_backward(ctx.plan, record, *given)
+        return (None,) * 6 + tuple(view if wanted else None for view, wanted in zip(gradients.views, ctx.needs_input_grad[6:]))
+
+
+def mlp_train_apply(plan: MlpTrainPlan, atom_types, x, l, time, sigma):
+    """(logits, score_x, score_l) with a grad_fn that reaches the plan's parameters (raw logits: the caller fills the MASK class)."""
+    return _MlpTrainFunction.apply(plan, atom_types, x, l, time, sigma, *plan.parameters)
+
+
+NOISE_WORKSPACE_MAX_FLOATS = 1 << 28       # 1 GiB cap; longer segments are split into several launches by the library
 NOISE_WORKSPACE_MIN_ITERATIONS = 1024       # first allocation holds at least this many iterations (within the cap)
 
 

@@ -1,4 +1,4 @@
-"""MLP score network (plugin of the ScoreNetwork API; PyTorch forward).
+"""MLP score network (plugin of the ScoreNetwork API; PyTorch forward, and the fused HIP forward and backward for training).
 
 Same hyper-parameters, parameter names (state_dict keys) and function as the reference's MLPScoreNetwork
 (src/.../models/score_networks/mlp_score_network.py:18-370), so reference checkpoints load with
@@ -36,7 +36,14 @@ class MLPScoreNetworkParameters(ScoreNetworkParameters):
 
 
 class MLPScoreNetwork(ScoreNetwork):
-    """Flattened-configuration MLP: inputs (cos 2 pi x, sin 2 pi x), sigma, t, one-hot(a), lattice."""
+    """Flattened-configuration MLP: inputs (cos 2 pi x, sin 2 pi x), sigma, t, one-hot(a), lattice.
+
+    fused_training = False   True: a forward in grad mode that the fused training kernels cover (_fused_training_covers) is one
+                             launch of mdx_mlp_train_forward on the module's own parameters, and its backward the two launches of
+                             mdx_mlp_train_backward, whose per-parameter gradients autograd accumulates into .grad as it does
+                             any other.  Every other forward, and every forward with the default, is the PyTorch code below."""
+
+    fused_training = False
 
     def __init__(self, hyper_params: MLPScoreNetworkParameters):
         super().__init__(hyper_params)
@@ -91,7 +98,32 @@ class MLPScoreNetwork(ScoreNetwork):
         assert batch[NOISY_AXL_COMPOSITION].X.shape[1] == self._natoms, \
             "The dimension corresponding to the number of atoms is not consistent with the configuration."
 
+    def _fused_training_covers(self, batch: Dict[AnyStr, torch.Tensor], conditional: bool) -> bool:
+        """Does this forward go through the fused training kernels?  With `fused_training` set: grad mode on, an unconditional
+        call of the plain network (no permutation symmetrisation, no prefactor), float32 device tensors, and no batch tensor
+        that requires grad (the kernels produce no input gradient)."""
+        if not self.fused_training or conditional or not torch.is_grad_enabled():
+            return False
+        if self.use_permutation_invariance or self.use_time_dependent_prefactor:
+            return False
+        comp = batch[NOISY_AXL_COMPOSITION]
+        floats = (comp.X, comp.L, batch[TIME], batch[NOISE])
+        if not (comp.A.is_cuda and all(t.is_cuda and t.dtype == torch.float32 and not t.requires_grad for t in floats)):
+            return False
+        return self.output_X_layer.weight.is_cuda
+
+    def _fused_single(self, batch: Dict[AnyStr, torch.Tensor]) -> AXL:
+        """_single(unconditional) by mdx_mlp_train_forward, with a grad_fn whose backward is mdx_mlp_train_backward."""
+        from ... import kernels
+        comp = batch[NOISY_AXL_COMPOSITION]
+        plan = kernels.mlp_train_plan(self)
+        logits, score_x, score_l = kernels.mlp_train_apply(plan, comp.A.long().contiguous(), comp.X.contiguous(), comp.L.contiguous(),
+                                                           batch[TIME].contiguous(), batch[NOISE].contiguous())
+        return AXL(A=logits, X=score_x, L=score_l)
+
     def _forward_unchecked(self, batch: Dict[AnyStr, torch.Tensor], conditional: bool = False) -> AXL:
+        if self._fused_training_covers(batch, conditional):
+            return self._fused_single(batch)
         if not self.use_permutation_invariance:
             return self._single(batch[NOISY_AXL_COMPOSITION], batch, conditional)
         # s_sym(x) = 1/|G| sum_g g^-1 . s(g . x)   (:228-262)

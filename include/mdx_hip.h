@@ -873,6 +873,55 @@ MDX_API int mdx_mlp_forward(const mdx_mlp_t* mlp_host, const int64_t* atom_types
                             const float* time, const float* sigma, int64_t batch, float* logits_out,
                             float* score_x_out, float* score_l_out, mdx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Training the MLP score network (csrc/mdx_mlp_train.hip): the same cover as mdx_mlp_forward (MLPScoreNetwork._single,
+ * unconditional, no permutation symmetrisation, no time prefactor; n_hidden <= MDX_MLP_MAX_HIDDEN, C <= MDX_MAX_CLASSES), on the
+ * module's OWN parameters: nn.Linear layout, weight [out, in] and bias [out], float32, contiguous.  Nothing is copied or packed,
+ * so an optimizer step between two calls is seen by the next one.
+ *   shape_host int32 [MDX_MLP_TRAIN_SHAPE_COUNT], host memory: number_of_atoms N, spatial_dimension d, num_classes C,
+ *       hidden_size H, n_hidden, then the embedding sizes e_coordinates, e_noise, e_time, e_atom_type, e_lattice.
+ *       Below nd = N d, nl = d (d + 1) / 2, F0 = e_coordinates + e_noise + e_time + N e_atom_type + e_lattice.
+ *   addresses uint64 [2 (5 + n_hidden + 3)], device memory: (weight, bias) of the layers in the order coordinates, noise, time,
+ *       atom type, lattice embedding, hidden 0 .. n_hidden - 1, output A, X, L: the order named_parameters() gives the
+ *       parameters the unconditional forward reads.  The flat gradient buffer holds them in this order, each tensor row-major:
+ *       mdx_mlp_train_parameter_count floats.
+ *
+ * mdx_mlp_train_forward: one wavefront per structure, activations in LDS, a layer's weights staged transposed into LDS (odd row
+ * length: no bank conflict in the store or in the layer loop), binary32 without contraction, the row sums and the SiLU of
+ * mdx_mlp_forward.  time, sigma: [B, 1].  Writes the RAW head outputs -- logits [B, N, C] WITHOUT the -inf of the MASK class,
+ * score_x [B, N, d], score_l [B, nl] -- and the activation record [B, mdx_mlp_train_record_floats], per structure, float32, the
+ * value the forward fed to every Linear:
+ *   cos 2 pi x [nd] | sin 2 pi x [nd] | sigma | time | atom classes [N] (as floats; clamped to [0, C)) | lattice [nl] |
+ *   the concatenated features [F0] (input of hidden 0) | the input of hidden k [H], k = 1 .. n_hidden - 1 | the input of the
+ *   heads [H] | the pre-activation z_k [H] of every hidden layer that goes through SiLU, k = 0 .. n_hidden - 2.
+ * MDX_ERR_UNSUPPORTED when the largest staged layer and the wavefronts' vectors exceed 128 KiB of LDS.
+ *
+ * mdx_mlp_train_backward: the gradient of every parameter from the record and the three output cotangents (each nullable: a
+ * part that is absent contributes nothing); no input gradient.  Two launches, no atomics, no ticket.
+ *   1. One workgroup per slab of MDX_MLP_TRAIN_STRUCTURES_PER_SLAB consecutive structures.  Per structure, one wavefront, in
+ *      binary64: delta_in[i] = sum_o W[o, i] delta[o] with o in index order, through the heads (A, X, L in that order), then per
+ *      hidden layer times silu'(z) = s (1 + z (1 - s)), s = 1 / (1 + exp(-z)), from the saved binary32 z, down to the features.
+ *      Then every gradient element, owned by one thread: dW[o, i] = sum_b delta_b[o] a_b[i], db[o] = sum_b delta_b[o] over the
+ *      slab's structures in index order (the atom-type embedding: structures in order, each one's atoms in order, the one-hot
+ *      input as 1.0 / 0.0), a_b the record's binary32 value widened -- delta is never rounded to binary32 -- into the slab's
+ *      part of workspace f64 [mdx_mlp_train_workspace_doubles] = [ceil(B / slab), parameter count].
+ *   2. Per element: the slabs in slab order, times scale, plus the buffer's old value when accumulate != 0, all in binary64,
+ *      rounded to binary32 ONCE into gradients_inout.  Every element is written, every workspace entry is written first.
+ * The same bits on every launch and under graph replay.  Non-finite values propagate; there is no status bit. */
+#define MDX_MLP_TRAIN_SHAPE_COUNT 10
+#define MDX_MLP_TRAIN_STRUCTURES_PER_SLAB 8
+MDX_API int64_t mdx_mlp_train_record_floats(const int32_t* shape_host);
+MDX_API int64_t mdx_mlp_train_parameter_count(const int32_t* shape_host);
+MDX_API int64_t mdx_mlp_train_workspace_doubles(const int32_t* shape_host, int64_t batch);
+MDX_API int mdx_mlp_train_forward(const int32_t* shape_host, const uint64_t* addresses, const int64_t* atom_types,
+                                  const float* x, const float* l, const float* time, const float* sigma, int64_t batch,
+                                  float* logits_out, float* score_x_out, float* score_l_out, float* record_out,
+                                  mdx_stream_t stream);
+MDX_API int mdx_mlp_train_backward(const int32_t* shape_host, const uint64_t* addresses, const float* record,
+                                   const float* grad_logits, const float* grad_x, const float* grad_l, int64_t batch,
+                                   double* workspace, int accumulate, double scale, float* gradients_inout,
+                                   mdx_stream_t stream);
+
 /* The whole sampling loop of LangevinGenerator.sample_from_noisy_composition
  * (generators/predictor_corrector_axl_generator.py:145-160 with langevin_generator.py:536-805) in ONE launch for an
  * MLP score network: every wavefront owns one structure, keeps its composition in LDS, and runs
