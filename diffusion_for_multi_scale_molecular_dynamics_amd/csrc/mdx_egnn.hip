@@ -1,4 +1,6 @@
-// EGNN helpers behind the C ABI: the passes around the MFMA kernels of mdx_egnn_chain.hip that PyTorch cannot fuse.
+// EGNN helpers behind the C ABI: the passes around the MFMA kernels of mdx_egnn_chain.hip that PyTorch cannot fuse -- the
+// network's per-node inputs and outputs and the segment kernels of the unfused path.  (The per-node passes that follow the edge
+// chain inside a graph layer are mdx_egnn_node.hip.)
 // (Rounds 1-4 also wrapped a hipBLASLt GEMM with a bias + SiLU epilogue here, mdx_linear_act, for layer shapes the edge chain
 // did not cover; since round 5 every option of the reference's E_GCL runs on the hand-written chain and the library links no
 // vendor GEMM -- shapes outside the chain's widths stay plain PyTorch modules on the caller's side.)
@@ -13,11 +15,7 @@
 #include "../../include/mdx_hip.h"
 #include "mdx_launch.hpp"
 
-// (named, not `using namespace`: this unit has a wave_sum of its own, on DPP adds)
-using mdx::as_stream;
-using mdx::kBlock;
-using mdx::kWave;
-using mdx::launch_status;
+using namespace mdx;
 
 namespace {
 
@@ -78,7 +76,7 @@ __global__ __launch_bounds__(kBlock) void egnn_node_inputs_kernel(const float* _
                                                                   const float* __restrict__ b2, int H2, float* __restrict__ h2,
                                                                   const uint32_t* __restrict__ table_key)
 {
-    if (mdx::table_is_current(table_key, sigma)) return; // (the grid's class nodes of a table that is still valid)
+    if (table_is_current(table_key, sigma)) return; // (the grid's class nodes of a table that is still valid)
     const int64_t stride = (int64_t)gridDim.x * blockDim.x, t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     // a second linear map of the same [sigma | one_hot] input (nullable): the first graph layer's per-node projections,
     // with w2 = P W, b2 = P b formed once on the host -- P (W x + b) without the [n_nodes, H] x [H, 2H] product
@@ -145,7 +143,7 @@ __global__ __launch_bounds__(kBlock) void egnn_node_inputs_rows_kernel(const flo
                                                                        float* __restrict__ h2,
                                                                        const uint32_t* __restrict__ table_key)
 {
-    if (mdx::table_is_current(table_key, sigma)) return; // (the grid's class nodes of a table that is still valid)
+    if (table_is_current(table_key, sigma)) return; // (the grid's class nodes of a table that is still valid)
     extern __shared__ float tables[];                   // [ (1 + F) H | (1 + F) H2 ]
     float* t1 = tables;
     float* t2 = tables + (1 + F) * H;
@@ -221,20 +219,8 @@ __global__ __launch_bounds__(kBlock) void egnn_scores_kernel(const float* __rest
 //                                           logit set to -inf (score_network.py:183-185) when mask_class >= 0
 //   scores[i, :]                            as egnn_scores_kernel
 //   zero_out[0 .. n_zero)                   the all-zero lattice output of the network (egnn_score_network.py:299-303)
-// A row of h is read once as 16-byte lane loads; the C <= kMaxClasses dot products share it and end in a butterfly.
-// sum over the 64 lanes with DPP adds (rows of 16, then lane 15 / 31 of the rows below; the total is lane 63's), handed to every
-// lane through a scalar register: no LDS permutes, a fixed order
-__device__ __forceinline__ float wave_sum(float v)
-{
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x111, 0xf, 0xf, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x112, 0xf, 0xf, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x114, 0xf, 0xf, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x118, 0xf, 0xf, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xa, 0xf, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x143, 0xc, 0xf, false));
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-
+// A row of h is read once as 16-byte lane loads; the C <= kMaxClasses dot products share it and end in a wavefront total
+// (wave_total_dpp).
 constexpr int kMaxClasses = 8;
 
 __global__ __launch_bounds__(kBlock) void egnn_outputs_kernel(const float* __restrict__ z, const float* __restrict__ x_hat,
@@ -291,7 +277,7 @@ __global__ __launch_bounds__(kBlock) void egnn_outputs_kernel(const float* __res
 #pragma unroll
                 for (int m = 0; m < kNodesPerWave; ++m) {
                     float v = part[m][c];
-                    if (c != mask_class) v = wave_sum(v);
+                    if (c != mask_class) v = wave_total_dpp(v);
                     if (lane == 0 && node0 + m < n_nodes) logits[(node0 + m) * C + c] = (c == mask_class) ? -__builtin_inff() : v + cb[c];
                 }
             }
@@ -329,7 +315,7 @@ __global__ __launch_bounds__(kBlock) void egnn_coord_head_kernel(const float* __
             return part;
         };
         auto finish = [&](int64_t e, float part) {
-            part = mdx::wave_sum(part);                     // the xor butterfly, not the DPP sum above
+            part = wave_sum(part);                          // (the xor butterfly, as ever: not the DPP total)
             if (lane < d) acc += coord_diff[e * d + lane] * part;
         };
         int64_t e = e0;
@@ -383,13 +369,6 @@ int mdx_egnn_message_input(const float* node_proj, const int64_t* edges, const f
     hipLaunchKernelGGL(egnn_message_input_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream),
                        node_proj, edges, radial, bias, w_radial, n_edges, H, silu, out);
     return launch_status();
-}
-
-static unsigned node_grid(int64_t n_nodes)
-{
-    int64_t blocks = (n_nodes * kWave + kBlock - 1) / kBlock;       // one wavefront per node
-    if (blocks > 16384) blocks = 16384;
-    return (unsigned)(blocks < 1 ? 1 : blocks);
 }
 
 int mdx_egnn_node_inputs(const float* x, const float* k_vectors, int n_k, const float* sigma, int atoms_per_structure,

@@ -39,6 +39,10 @@
 //               instruction brings the exponent back (Scale below).  Scaling by a power of two commutes with every
 //               rounding involved, so data of order one gives the same bits as without it.
 //               Magnitudes above the f16 range set MDX_STATUS_EGNN_F16_RANGE (the caller falls back to PREC 0).
+//
+// This unit holds the chain, its weight image and their entry points (mdx_egnn_chain_image_bytes, mdx_egnn_chain_pack,
+// mdx_egnn_edge_chain(_keyed), mdx_egnn_chain_adapt_activation_exponents, mdx_mlp_chain_rows, mdx_node_mlp_rows*) and nothing else:
+// it is compiled once per chain unit (this one, the attention unit, the self-checking build) and for every variant of tools/.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -1614,164 +1618,9 @@ __global__ __launch_bounds__(256) void egnn_chain_pack_kernel(PackArgs p)
     }
 }
 
-// The two per-edge options of E_GCL's coordinate update (models/egnn.py:128-131, 234-264), applied where the head's scalar meets
-// the coordinate difference:
-//   MDX_EGNN_COORD_TANH       the coordinate MLP ends in nn.Tanh: s_e <- tanh(s_e)
-//   MDX_EGNN_COORD_NORMALIZE  coord_diff <- f(r^2) coord_diff, f(r^2) = tanh(r^2) / sqrt(r^2 + epsilon^2), epsilon = 1e-8, r^2 the
-//                             squared length of coord_diff summed in component order (normalize_radial_norm)
-// trans = (f coord_diff) s, in the reference's order of operations.
-__device__ __forceinline__ float coord_head_value(float s, int flags) { return (flags & MDX_EGNN_COORD_TANH) ? tanhf(s) : s; }
-__device__ __forceinline__ float normalize_factor(float r2) { return tanhf(r2) / sqrtf(r2 + 1.0e-16f); }
-
-// coord_out[i,:] = coord[i,:] + scale_i sum_{e in segment i} (coord[i,:] - coord[dst_e,:]) * s_e
-__global__ __launch_bounds__(256) void egnn_coord_aggregate_kernel(const float* __restrict__ s, const float* __restrict__ coord,
-                                                                   const int64_t* __restrict__ edges,
-                                                                   const int64_t* __restrict__ offsets,
-                                                                   const int64_t* __restrict__ degree, int64_t n_nodes, int D,
-                                                                   int mean, int flags, float* __restrict__ out)
-{
-    const int64_t total = n_nodes * D;
-    for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t node = idx / D;
-        const int k = (int)(idx - node * D);
-        const int64_t e0 = offsets[node], deg = degree[node];
-        const float ci = coord[idx];
-        float acc = 0.0f;
-        for (int64_t e = e0; e < e0 + deg; ++e) {
-            const int64_t dst = edges[2 * e + 1];
-            float diff = ci - coord[dst * D + k];
-            if (flags & MDX_EGNN_COORD_NORMALIZE) {
-                float r2 = 0.0f;
-                for (int j = 0; j < D; ++j) {
-                    const float dj = coord[node * D + j] - coord[dst * D + j];
-                    r2 += dj * dj;
-                }
-                diff = normalize_factor(r2) * diff;
-            }
-            acc += diff * coord_head_value(s[e], flags);
-        }
-        if (mean && deg > 0) acc = acc / (float)deg;          // (a true division, as unsorted_segment_mean's: egnn_utils.py:66-68)
-        out[idx] = ci + acc;
-    }
-}
-
-// out[i,:] = (1/degree_i if mean) x sum of node i's pieces, in increasing edge order: the boundary rows e / 16 of its edges
-// e = 15 mod 16 and, when its last edge is not one of those, its own row boundary_rows + i (the compact layout the edge
-// chain writes, aggregate_pieces).  One wavefront per node, 16 bytes per lane.
-// `left` (nullable): out rows are [left[i,:] | sum_i] of width 2 H -- the input of the node MLP's first layer (h | agg), written
-// in the one pass over the nodes instead of a concatenation afterwards.
-__global__ __launch_bounds__(256) void segment_combine_kernel(const float* __restrict__ pieces, const int64_t* __restrict__ offsets,
-                                                              const int64_t* __restrict__ degree, int64_t n_nodes, int H,
-                                                              int mean, float* __restrict__ out, const float* __restrict__ left,
-                                                              int64_t boundary_rows)
-{
-    const int lane = threadIdx.x % kWave;
-    const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave;
-    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
-    const int quads = H >> 2;
-    for (int64_t node = wave; node < n_nodes; node += n_waves) {
-        const int64_t e0 = offsets[node], deg = degree[node], e1 = e0 + deg;
-        const float count = (mean && deg > 0) ? (float)deg : 1.0f;      // the mean DIVIDES by the count (egnn_utils.py:66-68)
-        // the node's last piece: a boundary row if its last edge is 15 mod 16, else the node's own row
-        const int64_t last_row = ((e1 - 1) & 15) == 15 ? ((e1 - 1) >> 4) : boundary_rows + node;
-        for (int q = lane; q < quads; q += kWave) {
-            f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-            for (int64_t e = e0 | 15; e < e1 - 1; e += 16) acc += reinterpret_cast<const f32x4*>(pieces + (e >> 4) * H)[q];
-            if (deg > 0) acc += reinterpret_cast<const f32x4*>(pieces + last_row * H)[q];
-            if (mean) acc = acc / count;
-            if (left) {
-                reinterpret_cast<f32x4*>(out + node * 2 * H)[q] = reinterpret_cast<const f32x4*>(left + node * H)[q];
-                reinterpret_cast<f32x4*>(out + node * 2 * H + H)[q] = acc;
-            } else {
-                reinterpret_cast<f32x4*>(out + node * H)[q] = acc;
-            }
-        }
-    }
-}
-
-// segment_combine_kernel and egnn_coord_aggregate_kernel as ONE pass over the nodes (one wavefront per node): the message part
-// exactly as segment_combine_kernel; the coordinate part with the node's edges dealt to the lanes (edge offset + lane, + 64, ...),
-// D partial sums per lane and a butterfly over the wavefront -- a fixed order, no atomics.  D <= 8.
-__global__ __launch_bounds__(256) void egnn_node_gather_kernel(const float* __restrict__ pieces, const int64_t* __restrict__ offsets,
-                                                               const int64_t* __restrict__ degree, int64_t n_nodes, int H,
-                                                               int mean_messages, float* __restrict__ out,
-                                                               const float* __restrict__ left, int64_t boundary_rows,
-                                                               const float* __restrict__ s, const float* __restrict__ coord,
-                                                               const int64_t* __restrict__ edges, int D, int mean_coords,
-                                                               int flags, float* __restrict__ coord_out)
-{
-    const int lane = threadIdx.x % kWave;
-    const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave;
-    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
-    const int quads = H >> 2;
-    for (int64_t node = wave; node < n_nodes; node += n_waves) {
-        const int64_t e0 = offsets[node], deg = degree[node], e1 = e0 + deg;
-        // coordinates first (their loads are the long-latency ones)
-        float part[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ci[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) ci[k] = k < D ? coord[node * D + k] : 0.0f;
-        for (int64_t e = e0 + lane; e < e1; e += kWave) {
-            const int64_t dst = edges[2 * e + 1];
-            const float se = coord_head_value(s[e], flags);
-            if (flags & MDX_EGNN_COORD_NORMALIZE) {          // (uniform per launch)
-                float diff[8], r2 = 0.0f;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    diff[k] = k < D ? ci[k] - coord[dst * D + k] : 0.0f;
-                    if (k < D) r2 += diff[k] * diff[k];
-                }
-                const float f = normalize_factor(r2);
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-                    if (k < D) part[k] += (f * diff[k]) * se;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-                    if (k < D) part[k] += (ci[k] - coord[dst * D + k]) * se;
-            }
-        }
-        // messages (pieces == null, uniform per launch: the caller reads the coordinates alone -- the last graph layer of a
-        // forward whose atom-type logits nobody reads)
-        const float count = (mean_messages && deg > 0) ? (float)deg : 1.0f;      // (a true division: egnn_utils.py:66-68)
-        const int64_t last_row = ((e1 - 1) & 15) == 15 ? ((e1 - 1) >> 4) : boundary_rows + node;
-        for (int q = lane; pieces && q < quads; q += kWave) {
-            f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-            for (int64_t e = e0 | 15; e < e1 - 1; e += 16) acc += reinterpret_cast<const f32x4*>(pieces + (e >> 4) * H)[q];
-            if (deg > 0) acc += reinterpret_cast<const f32x4*>(pieces + last_row * H)[q];
-            if (mean_messages) acc = acc / count;
-            if (left) {
-                reinterpret_cast<f32x4*>(out + node * 2 * H)[q] = reinterpret_cast<const f32x4*>(left + node * H)[q];
-                reinterpret_cast<f32x4*>(out + node * 2 * H + H)[q] = acc;
-            } else {
-                reinterpret_cast<f32x4*>(out + node * H)[q] = acc;
-            }
-        }
-        // sum over the wavefront with DPP adds (rows of 16, then lane 15 / 31 of the rows below: the total is lane 63's), read
-        // back through a scalar register -- no LDS permutes; a fixed order
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            if (k < D) {
-                float v = part[k];
-                v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x111, 0xf, 0xf, false));
-                v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x112, 0xf, 0xf, false));
-                v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x114, 0xf, 0xf, false));
-                v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x118, 0xf, 0xf, false));
-                v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xa, 0xf, false));
-                v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x143, 0xc, 0xf, false));
-                part[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-            }
-        }
-        if (lane < D) {
-            float total = 0.0f, mine = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                if (k == lane) { total = part[k]; mine = ci[k]; }
-            }
-            if (mean_coords && deg > 0) total = total / (float)deg;
-            coord_out[node * D + lane] = mine + total;
-        }
-    }
-}
+// (The weight-image kernels above stay in this unit: their index formulas are the other half of the chain's fragment reads.
+// The per-node passes that follow the chain -- segment_combine_kernel, egnn_coord_aggregate_kernel, egnn_node_gather_kernel --
+// have nothing to do with the matrix cores and sit in mdx_egnn_node.hip.)
 
 template <int H, int PREC, int MODE, bool ATT = false>
 int launch_chain(const ChainArgs& a, int layers, hipStream_t st)
@@ -1933,46 +1782,6 @@ int mdx_egnn_chain_adapt_activation_exponents(uint32_t* maxima_inout, int count,
     return hipGetLastError() == hipSuccess ? MDX_OK : MDX_ERR_HIP;
 }
 
-int64_t mdx_egnn_piece_rows(int64_t n_edges, int64_t n_nodes)
-{
-    if (n_edges < 0 || n_nodes < 0) return -1;
-    return ((n_edges + 15) >> 4) + n_nodes;
-}
-
-int mdx_segment_combine(const float* pieces, int64_t n_edges, const int64_t* offsets, const int64_t* degree, int64_t n_nodes,
-                        int H, int mean, const float* left, float* out, mdx_stream_t stream)
-{
-    if (n_nodes < 0 || H < 4 || n_edges < 0) return MDX_ERR_INVALID_ARG;
-    if (H & 3) return MDX_ERR_UNSUPPORTED;
-    if (n_nodes == 0) return MDX_OK;
-    if (!pieces || !offsets || !degree || !out) return MDX_ERR_INVALID_ARG;
-    int64_t blocks = (n_nodes * kWave + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(segment_combine_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       pieces, offsets, degree, n_nodes, H, mean, out, left, (n_edges + 15) >> 4);
-    return hipGetLastError() == hipSuccess ? MDX_OK : MDX_ERR_HIP;
-}
-
-int mdx_egnn_node_gather(const float* pieces, int64_t n_edges, const int64_t* offsets, const int64_t* degree, int64_t n_nodes,
-                         int H, int mean_messages, const float* left, float* out, const float* edge_scalar, const float* coord,
-                         int coord_dimension, const int64_t* edges, int mean_coords, int coord_flags, float* coord_out,
-                         mdx_stream_t stream)
-{
-    if (n_nodes < 0 || H < 4 || n_edges < 0 || coord_dimension < 1) return MDX_ERR_INVALID_ARG;
-    if (coord_flags & ~(MDX_EGNN_COORD_NORMALIZE | MDX_EGNN_COORD_TANH)) return MDX_ERR_INVALID_ARG;
-    if ((H & 3) || coord_dimension > 8) return MDX_ERR_UNSUPPORTED;
-    if (n_nodes == 0) return MDX_OK;
-    if (!offsets || !degree || !edge_scalar || !coord || !edges || !coord_out) return MDX_ERR_INVALID_ARG;
-    // pieces == out == left == null: the coordinate half alone (the same bits as with the message half)
-    if (pieces ? !out : (out || left)) return MDX_ERR_INVALID_ARG;
-    int64_t blocks = (n_nodes * kWave + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(egnn_node_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       pieces, offsets, degree, n_nodes, H, mean_messages, out, left, (n_edges + 15) >> 4, edge_scalar, coord, edges,
-                       coord_dimension, mean_coords, coord_flags, coord_out);
-    return hipGetLastError() == hipSuccess ? MDX_OK : MDX_ERR_HIP;
-}
-
 int mdx_mlp_chain_rows(const mdx_egnn_chain_t* c, const float* x, const float* residual, int64_t n_rows,
                        const int64_t* n_rows_dev, float* out, uint32_t* status, mdx_stream_t stream)
 {
@@ -2061,21 +1870,6 @@ static int node_mlp_rows(const mdx_egnn_chain_t* c, const float* node_in, int64_
     }
 #undef MDX_NODE_CASE
     return MDX_ERR_UNSUPPORTED;
-}
-
-int mdx_egnn_coord_aggregate(const float* edge_scalar, const float* coord, int coord_dimension, const int64_t* edges,
-                             const int64_t* offsets, const int64_t* degree, int64_t n_nodes, int mean, int coord_flags,
-                             float* coord_out, mdx_stream_t stream)
-{
-    if (n_nodes < 0 || coord_dimension < 1) return MDX_ERR_INVALID_ARG;
-    if (coord_flags & ~(MDX_EGNN_COORD_NORMALIZE | MDX_EGNN_COORD_TANH)) return MDX_ERR_INVALID_ARG;
-    if (n_nodes == 0) return MDX_OK;
-    if (!edge_scalar || !coord || !edges || !offsets || !degree || !coord_out) return MDX_ERR_INVALID_ARG;
-    int64_t blocks = (n_nodes * coord_dimension + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(egnn_coord_aggregate_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       edge_scalar, coord, edges, offsets, degree, n_nodes, coord_dimension, mean, coord_flags, coord_out);
-    return hipGetLastError() == hipSuccess ? MDX_OK : MDX_ERR_HIP;
 }
 
 }  // extern "C"

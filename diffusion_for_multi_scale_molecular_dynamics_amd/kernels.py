@@ -2015,6 +2015,7 @@ def egnn_edge_chain(pack: EdgeChainPack, node_proj, coord, edges, status=None, n
     return messages, scalar
 
 
+# ---- the per-node passes behind the edge chain (csrc/mdx_egnn_node.hip)
 def segment_combine(pieces, n_edges: int, offsets, degree, mean: bool, left=None) -> torch.Tensor:
     """Sum (or mean) over each node's edges from the piece sums of egnn_edge_chain(..., piece_sums=True) over `n_edges` edge
     rows (the capacity that call was given) -> [n_nodes, H]; with `left` [n_nodes, H]: [left | sums], [n_nodes, 2H] (the
@@ -2053,7 +2054,8 @@ def egnn_node_gather(pieces, n_edges: int, offsets, degree, mean_messages: bool,
     return out, coord_out
 
 
-# ---- the first graph layer on a distance grid (mdx_egnn_table_check / _gather)
+# ---- the first graph layer on a distance grid (mdx_egnn_table_check: csrc/mdx_egnn_table.hip; mdx_egnn_table_gather:
+# csrc/mdx_egnn_node.hip)
 TABLE_INV_SPACING = 256.0        # h = 2^-8 between the even grid points: rho_k = k h / 2, k^2 < 2^24 keeps rho_k^2 exact
 # largest midpoint error, relative to the class pair's largest |value|: the chain's own rounding noise sits at ~2e-6 of that
 # (exact-f32 and split-f16 alike, measured at C3 / C4 -- csrc/mdx_egnn_table.hip), so the check is set 8x above it; an

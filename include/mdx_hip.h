@@ -996,7 +996,9 @@ MDX_API int mdx_segment_rows(const float* data, const int64_t* offsets, const in
                              int mean, float* out, mdx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
- * Fused EGNN edge chain on the matrix cores (hand-written MFMA kernel, csrc/mdx_egnn_chain.hip): for every edge of the
+ * Fused EGNN edge chain on the matrix cores (hand-written MFMA kernel, csrc/mdx_egnn_chain.hip; the per-node passes behind
+ * it -- mdx_segment_combine, mdx_egnn_node_gather, mdx_egnn_coord_aggregate, mdx_egnn_table_gather -- are
+ * csrc/mdx_egnn_node.hip): for every edge of the
  * SORTED edge list, the whole per-edge part of E_GCL.forward (models/egnn.py:136-200, 232-289) in one launch --
  *   x0  = SiLU(node_proj[src,:H] + node_proj[dst,H:] + bias_in + |coord_src - coord_dst|^2 w_radial)   (first message layer)
  *   x   = SiLU(x W_l^T + b_l), l = 0 .. n_message_layers-1                  -> messages_out [E,H]
@@ -1072,7 +1074,7 @@ MDX_API int mdx_egnn_chain_pack(const float* const* weights_host, int n_layers, 
 MDX_API int mdx_egnn_edge_chain(const mdx_egnn_chain_t* chain_host, const float* node_proj, const float* coord,
                                 int coord_dimension, const int64_t* edges, int64_t n_edges, const int64_t* n_edges_dev,
                                 float* messages_out, float* edge_scalar_out, uint32_t* status, mdx_stream_t stream);
-/* Message aggregation without the [E,H] round trip: with message_mode = MDX_EGNN_MESSAGES_PIECE_SUMS the edge chain adds
+/* Message aggregation without the [E,H] round trip (the per-node side: csrc/mdx_egnn_node.hip): with message_mode = MDX_EGNN_MESSAGES_PIECE_SUMS the edge chain adds
  * the messages of a node's edges up INSIDE the kernel, per group of 16 consecutive edge rows (the list is sorted by source),
  * and writes only those sums, into a COMPACT buffer of mdx_egnn_piece_rows(n_edges, n_nodes) = ceil(n_edges / 16) + n_nodes
  * rows (n_edges = the capacity passed to mdx_egnn_edge_chain): the sum over the edges of node i inside group
@@ -1101,7 +1103,8 @@ MDX_API int mdx_egnn_node_gather(const float* pieces, int64_t n_edges, const int
                                  const float* edge_scalar, const float* coord, int coord_dimension, const int64_t* edges,
                                  int mean_coords, int coord_flags, float* coord_out, mdx_stream_t stream);
 
-/* The first graph layer of a sampler forward on a distance grid (csrc/mdx_egnn_table.hip).  With one
+/* The first graph layer of a sampler forward on a distance grid (the check: csrc/mdx_egnn_table.hip; the gather:
+ * csrc/mdx_egnn_node.hip).  With one
  * sigma per batch the layer's per-edge output (messages [H] and the coordinate head's raw scalar) is a function F_ab(rho) of the
  * class pair (a, b) -- atom type, MASK = n_classes - 1 -- and of rho = sqrt(|c_i - c_j|^2).  `table` [n_classes^2 K, H] and
  * `table_scalar` [n_classes^2 K] are mdx_egnn_edge_chain's MDX_EGNN_MESSAGES_ROWS outputs on the grid problem: class pair

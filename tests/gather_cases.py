@@ -1,5 +1,5 @@
 """Inputs and float64 restatements for the per-node end of an EGNN layer (segment_combine_kernel, egnn_node_gather_kernel,
-egnn_coord_aggregate_kernel: csrc/mdx_egnn_chain.hip; egnn_table_gather_kernel / egnn_table_check_kernel: csrc/mdx_egnn_table.hip).
+egnn_coord_aggregate_kernel, egnn_table_gather_kernel: csrc/mdx_egnn_node.hip; egnn_table_check_kernel: csrc/mdx_egnn_table.hip).
 
 Everything here is numpy / torch on the CPU and states a contract from its documentation (include/mdx_hip.h), not from the
 kernel that implements it: the compact piece layout, the coordinate update, the cubic interpolation on the distance grid."""

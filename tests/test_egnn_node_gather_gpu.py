@@ -1,4 +1,4 @@
-"""mdx_segment_combine, mdx_egnn_node_gather and mdx_egnn_coord_aggregate (csrc/mdx_egnn_chain.hip), each called directly, against
+"""mdx_segment_combine, mdx_egnn_node_gather and mdx_egnn_coord_aggregate (csrc/mdx_egnn_node.hip), each called directly, against
 float64 restatements of their contracts (tests/gather_cases.py) with a bar per node and per column / component.
 
 The pieces are NOT the edge chain's: gather_cases.pieces_from_messages writes the documented compact layout on its own, with NaN

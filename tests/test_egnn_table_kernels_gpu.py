@@ -1,4 +1,5 @@
-"""kernels.egnn_table_gather and kernels.egnn_table_check (csrc/mdx_egnn_table.hip) called directly on synthetic tables: every
+"""kernels.egnn_table_gather (csrc/mdx_egnn_node.hip) and kernels.egnn_table_check (csrc/mdx_egnn_table.hip) called directly on
+synthetic tables: every
 (class pair, column) of the table is a random cubic in rho, so the 4-point interpolation is exact up to rounding and a float64
 interpolation of the same binary32 table (gather_cases.table_reference) is a reference with a bar per node and column."""
 import functools

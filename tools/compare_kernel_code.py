@@ -8,8 +8,9 @@ Makefile's CXXFLAGS plus --save-temps -Rpass-analysis=kernel-resource-usage; the
 from its label to .end_amdhsa_kernel, so the kernel descriptor is compared too; a device function the inliner kept: to its end
 label), names demangled, comments dropped, and normalised as in profiles/r09_unit_split.md: the numbers of .LBB<n>_ / .Lfunc_* /
 .Ltmp labels and the `mdx::` / `(anonymous namespace)::` components of names.  Per unit it prints what is identical, different,
-new or gone, with the compiler's resource remarks beside what is not identical.  Exit status 1 when anything differs, is new
-or is gone.
+new or gone, with the compiler's resource remarks beside what is not identical.  A function that is gone from one unit and new
+under the same name in another is compared across the two and printed, where it left, as "moved, identical" or "moved,
+different".  Exit status 1 when anything differs, is new or is gone (a move that left the code identical is none of these).
 """
 import argparse
 import concurrent.futures
@@ -96,6 +97,14 @@ def instructions(body) -> int:
     return sum(1 for line in body if re.match(r"\s+[a-z]", line))
 
 
+def compared(name, args, old_body, new_body, old_remarks, new_remarks) -> str:
+    """The report of a function present on both sides: instruction counts, remarks, and --diff lines of the difference."""
+    return (f"{name}\n        instructions {instructions(old_body)} -> {instructions(new_body)}\n"
+            f"        {args.rev}: {old_remarks.get(name, 'no remark')}\n        tree: {new_remarks.get(name, 'no remark')}"
+            + "".join("\n        | " + line for line in list(difflib.unified_diff(old_body, new_body, args.rev, "tree", n=2,
+                                                                                  lineterm=""))[:args.diff]))
+
+
 def main() -> int:
     parser = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     parser.add_argument("rev")
@@ -117,33 +126,40 @@ def main() -> int:
             built = {(side, unit): pool.submit(compile_unit, csrc / f"{unit}.hip", scratch / "out" / side / unit)
                      for side, csrc in trees.items() for unit in units if (csrc / f"{unit}.hip").exists()}
             built = {key: job.result() for key, job in built.items()}
-    total = {"identical": 0, "different": 0, "new": 0, "gone": 0}
+    kinds = ("identical", "different", "moved, identical", "moved, different", "new", "gone")
+    report = {unit: {kind: {} for kind in kinds} for unit in units}          # unit -> kind -> {function name: text}
     for unit in units:
         old_code, old_remarks = built.get(("rev", unit), ({}, {}))
         new_code, new_remarks = built.get(("tree", unit), ({}, {}))
-        rows = {"identical": [], "different": [], "new": [], "gone": []}
+        rows = report[unit]
         for name in sorted(old_code.keys() | new_code.keys()):
             if name not in new_code:
-                rows["gone"].append(f"{name}\n        {args.rev}: {old_remarks.get(name, 'no remark')}")
+                rows["gone"][name] = f"{name}\n        {args.rev}: {old_remarks.get(name, 'no remark')}"
             elif name not in old_code:
-                rows["new"].append(f"{name}\n        tree: {new_remarks.get(name, 'no remark')}")
+                rows["new"][name] = f"{name}\n        tree: {new_remarks.get(name, 'no remark')}"
             elif old_code[name] != new_code[name] or old_remarks.get(name) != new_remarks.get(name):
-                rows["different"].append(f"{name}\n        instructions {instructions(old_code[name])} -> {instructions(new_code[name])}\n"
-                                         f"        {args.rev}: {old_remarks.get(name, 'no remark')}\n"
-                                         f"        tree: {new_remarks.get(name, 'no remark')}")
-                rows["different"][-1] += "".join("\n        | " + line for line in list(difflib.unified_diff(
-                    old_code[name], new_code[name], args.rev, "tree", n=2, lineterm=""))[:args.diff])
+                rows["different"][name] = compared(name, args, old_code[name], new_code[name], old_remarks, new_remarks)
             else:
-                rows["identical"].append(f"{name}\n        {new_remarks.get(name, 'no remark')}")
-        print(f"{unit}.hip: " + ", ".join(f"{len(names)} {kind}" for kind, names in rows.items()))
-        for kind in ("different", "new", "gone") + (("identical",) if args.identical else ()):
-            for row in rows[kind]:
+                rows["identical"][name] = f"{name}\n        {new_remarks.get(name, 'no remark')}"
+    # a function gone from one unit and new under the same name in another has moved: the pair is compared like any other and
+    # reported where it left (a second unit that lost the same function, a dead copy, keeps its "gone")
+    for unit in units:
+        for name in list(report[unit]["gone"]):
+            if to := next((other for other in units if name in report[other]["new"]), None):
+                (old_code, old_remarks), (new_code, new_remarks) = built[("rev", unit)], built[("tree", to)]
+                same = old_code[name] == new_code[name] and old_remarks.get(name) == new_remarks.get(name)
+                del report[unit]["gone"][name], report[to]["new"][name]
+                report[unit]["moved, identical" if same else "moved, different"][name] = f"{unit}.hip -> {to}.hip: " + compared(
+                    name, args, old_code[name], new_code[name], old_remarks, new_remarks)
+    for unit in units:
+        rows = report[unit]
+        print(f"{unit}.hip: " + ", ".join(f"{len(rows[kind])} {kind}" for kind in kinds if rows[kind] or "moved" not in kind))
+        for kind in kinds[1:] + (kinds[:1] if args.identical else ()):
+            for row in rows[kind].values():
                 print(f"    {kind}: {row}")
-        for kind, names in rows.items():
-            total[kind] += len(names)
+    total = {kind: sum(len(report[unit][kind]) for unit in units) for kind in kinds}
     print("all units: " + ", ".join(f"{count} {kind}" for kind, count in total.items()))
-    return 1 if total["different"] or total["new"] or total["gone"] else 0
-
+    return 1 if total["different"] or total["moved, different"] or total["new"] or total["gone"] else 0
 
 if __name__ == "__main__":
     sys.exit(main())
