@@ -26,6 +26,7 @@
 #include "../../include/mdx_hip.h"
 #include "mdx_launch.hpp"
 #include "mdx_math.hpp"
+#include "mdx_noisers.hpp"
 
 using namespace mdx;
 
@@ -277,7 +278,7 @@ __global__ __launch_bounds__(kBlock) void noise_coords_kernel(const float* x0, c
                                                               float* out)
 {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x)
-        out[i] = wrap01(x0[i] + sigma * z[i]);
+        out[i] = noised_relative_coordinate(x0[i], sigma, z[i]);
 }
 
 // the reference's own signatures: one sigma per element (noisers/relative_coordinates_noiser.py:33-67, lattice_noiser.py:47-81)
@@ -285,14 +286,14 @@ __global__ __launch_bounds__(kBlock) void noise_coords_sigmas_kernel(const float
                                                                      int64_t count, float* out)
 {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x)
-        out[i] = wrap01(x0[i] + sigmas[i] * z[i]);
+        out[i] = noised_relative_coordinate(x0[i], sigmas[i], z[i]);
 }
 
 __global__ __launch_bounds__(kBlock) void noise_lattice_kernel(const float* l0, const float* z, const float* sigmas_n,
                                                                int64_t count, float* out)
 {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x)
-        out[i] = sigmas_n[i] * z[i] + l0[i];
+        out[i] = noised_lattice_parameter(sigmas_n[i], z[i], l0[i]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1971,20 +1972,7 @@ __global__ __launch_bounds__(kMlpWaves* kWave) void mlp_pc_sample_kernel(MlpSamp
 // ---------------------------------------------------------------------------------------------------------------
 // F2 stand-alone and R1
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int noised_atom_type(int a0, const float* __restrict__ qbar, int C, const float* gum_u,
-                                                bool from_u)
-{
-    float best = 0.0f;
-    int arg = 0;
-    for (int c = 0; c < C; ++c) {
-        const float lq = logf_(qbar[a0 * C + c]);
-        const float gn = from_u ? gumbel_from_u(gum_u[c]) : gum_u[c];
-        const float v = lq + gn;
-        if (c == 0 || v > best || (v != v && best == best)) { best = v; arg = c; }
-    }
-    return arg;
-}
-
+// (noised_atom_type: mdx_noisers.hpp)
 // atom_stride: 0 = one [C,C] matrix for every atom, C*C = a matrix per atom (the reference's broadcast q_bar [..., C, C])
 __global__ __launch_bounds__(kBlock) void noise_atom_types_kernel(const int64_t* a0, const float* qbar, int64_t atom_stride,
                                                                   const float* u, int64_t n_atoms, int C, int64_t* out)
@@ -2233,6 +2221,7 @@ const char* mdx_status_string(int status)
         case MDX_STATUS_ANALYTICAL_COORDINATES: return "the relative coordinates should all be in [0, 1)";
         case MDX_STATUS_KS_NAN: return "a sample of the Kolmogorov-Smirnov metric holds a NaN";
         case MDX_STATUS_OPTIMIZER_NONFINITE: return "a gradient of the optimizer step is not finite";
+        case MDX_STATUS_NOISING_INDEX: return "a dataset row, time index or atom type of a training batch is out of range";
         default: return "unknown status";
     }
 }

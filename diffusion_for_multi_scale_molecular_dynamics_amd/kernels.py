@@ -242,6 +242,67 @@ def repaint_rows_per_sample(sched: DeviceSchedule, index_i: int, d_index, constr
          constrained_indices, counts, E, K, sample_environment, z, u, rng, B, N, d, x_inout, a_inout)
 
 
+NoisedTrainingBatch = namedtuple("NoisedTrainingBatch", ["x0", "a0", "l0", "time_indices", "time", "sigma", "xt", "at", "lt", "q",
+                                                         "q_bar", "q_bar_tm1"])
+NOISING_INDEX_MESSAGE = "a dataset row, a time index or an atom type of a training batch is outside its range"
+
+
+def noised_training_batch_buffers(batch: int, number_of_atoms: int, spatial_dimension: int, num_classes: int,
+                                  device) -> NoisedTrainingBatch:
+    """The twelve outputs of noise_training_batch for a batch of this size, uninitialised."""
+    B, N, d, Cn, nl = batch, number_of_atoms, spatial_dimension, num_classes, spatial_dimension * (spatial_dimension + 1) // 2
+    f = lambda *shape: torch.empty(*shape, dtype=F32, device=device)      # noqa: E731
+    i = lambda *shape: torch.empty(*shape, dtype=I64, device=device)      # noqa: E731
+    return NoisedTrainingBatch(x0=f(B, N, d), a0=i(B, N), l0=f(B, nl), time_indices=i(B), time=f(B), sigma=f(B), xt=f(B, N, d),
+                               at=i(B, N), lt=f(B, nl), q=f(B, Cn, Cn), q_bar=f(B, Cn, Cn), q_bar_tm1=f(B, Cn, Cn))
+
+
+def raise_noising_status(status: torch.Tensor):
+    """One host read of a status word mdx_noise_training_batch reported into: its bit is cleared, then raised."""
+    if _take_status_bits(status, _hip.STATUS_NOISING_INDEX) & _hip.STATUS_NOISING_INDEX:
+        raise IndexError(NOISING_INDEX_MESSAGE)
+
+
+def noise_training_batch(sched: DeviceSchedule, x0, a0, l0, batch: int, *, rows=None, row_offset: int = 0, cursor=None,
+                         time_indices=None, z=None, u=None, z_lattice=None, rng: Optional[Rng] = None,
+                         use_fixed_lattice_parameters: bool = False, out: Optional[NoisedTrainingBatch] = None,
+                         status: Optional[torch.Tensor] = None) -> NoisedTrainingBatch:
+    """`batch` rows of the device-resident dataset x0 f32 [M, N, d], a0 int64 [M, N], l0 f32 [M, d(d+1)/2], gathered and noised
+    in ONE launch (mdx_noise_training_batch), no host read.  Structure b is row rows[p] (int64, e.g. a permutation; None: p) at
+    p = row_offset + cursor * batch + b; `cursor` is an int32 device word or None (0).  `time_indices` int64 [batch], z
+    [batch, N, d], u [batch, N, C], z_lattice [batch, nl] are pre-drawn; each None is drawn on the device from `rng`, keyed by
+    the dataset row (include/mdx_hip.h).  `out` takes preallocated buffers (noised_training_batch_buffers), so that a captured
+    launch writes where the step reads.  `status`: the int32 device word MDX_STATUS_NOISING_INDEX is OR-ed into."""
+    _device_only("the training batch's noising", x0=x0, a0=a0, l0=l0, rows=rows, cursor=cursor, time_indices=time_indices, z=z, u=u,
+                 z_lattice=z_lattice, status=status, schedule=sched.time,
+                 **({} if out is None else {"out." + name: t for name, t in out._asdict().items()}))
+    if x0.dim() != 3 or tuple(a0.shape) != tuple(x0.shape[:2]):
+        raise ValueError(f"x0 has shape {tuple(x0.shape)} and a0 {tuple(a0.shape)}, expected [M, N, d] and [M, N]")
+    M, N, d = x0.shape
+    B, Cn, nl = int(batch), sched.num_classes, d * (d + 1) // 2
+    if tuple(l0.shape) != (M, nl):
+        raise ValueError(f"l0 has shape {tuple(l0.shape)}, expected {(M, nl)}")
+    if rng is None:
+        if time_indices is None or z is None or u is None or (z_lattice is None and not use_fixed_lattice_parameters):
+            raise ValueError("a draw that is not given needs the device RNG request `rng`")
+        rng = Rng(0, 0, 1, 0)
+    if rows is not None and rows.dim() != 1:
+        raise ValueError(f"rows has shape {tuple(rows.shape)}, expected [count]")
+    out = noised_training_batch_buffers(B, N, d, Cn, x0.device) if out is None else out
+    expected = dict(x0=(B, N, d), a0=(B, N), l0=(B, nl), time_indices=(B,), time=(B,), sigma=(B,), xt=(B, N, d), at=(B, N),
+                    lt=(B, nl), q=(B, Cn, Cn), q_bar=(B, Cn, Cn), q_bar_tm1=(B, Cn, Cn), time_indices_in=(B,), z=(B, N, d),
+                    u=(B, N, Cn), z_lattice=(B, nl))
+    given = dict(out._asdict(), time_indices_in=time_indices, z=z, u=u, z_lattice=z_lattice)
+    for name, t in given.items():
+        if t is not None and t.numel() != torch.Size(expected[name]).numel():
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {expected[name]}")
+    call("mdx_noise_training_batch", C.byref(sched.c_struct), x0, a0, l0, M, rows, 0 if rows is None else rows.numel(),
+         int(row_offset), cursor, time_indices, z, u, z_lattice, rng, B, N, d, float(root_of_atom_count(N, d)),
+         int(bool(use_fixed_lattice_parameters)), out.x0, out.a0, out.l0, out.time_indices, out.time, out.sigma, out.xt, out.at,
+         out.lt, out.q, out.q_bar, out.q_bar_tm1, status)
+    return out
+
+
 class ExcisionCapacityError(_hip.MdxError):
     """MDX_STATUS_EXCISE_CAPACITY: an environment holds more atoms than the call's capacity; call again with a larger one."""
 

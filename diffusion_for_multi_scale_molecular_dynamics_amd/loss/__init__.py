@@ -178,7 +178,8 @@ def optimisation_step(axl_network, noised_batch: Dict[str, Any], optimizer, loss
 
     With a FusedAdam the step, the clipping and the zeroing are its launches (the clipped values are used, `.grad` is never
     rewritten with them); any other optimizer gets torch's clip_grad_norm_, step() and zero_grad(set_to_none=False).  Nothing
-    is read from the device.  No epoch loop, data module, logging or checkpoint writing: those are the caller's."""
+    is read from the device.  The epoch loop and the data modules around it are training.fit's; logging and checkpoint writing
+    are the caller's."""
     if accumulate_grad_batches < 1:
         raise ValueError(f"accumulate_grad_batches is {accumulate_grad_batches}: it counts batches, so at least 1")
     output = training_loss(axl_network, noised_batch, loss_parameters, regularizer, current_epoch, kmax_target_score, conditional)

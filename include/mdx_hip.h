@@ -80,6 +80,9 @@ extern "C" {
                                             Kolmogorov-Smirnov distance of such a sample is NaN); the output is unspecified  */
 #define MDX_STATUS_OPTIMIZER_NONFINITE 524288u /* mdx_adam_step: a scaled, clipped gradient that is not finite; the arithmetic
                                             goes on as torch's does (the NaN propagates into the parameter and its state)    */
+#define MDX_STATUS_NOISING_INDEX 1048576u /* mdx_noise_training_batch: a batch position or a dataset row outside its range, a given
+                                            time index outside [0, T), or an atom type outside [0, C - 1) (MASK included); the
+                                            index is clamped into its range before it is used, so nothing is read out of bounds */
 
 #define MDX_MAX_CLASSES 8      /* C supported by the fused atom-type kernels */
 #define MDX_PREDICTOR 0
@@ -100,6 +103,10 @@ extern "C" {
 #define MDX_TAG_FILL_UNIFORM 11
 #define MDX_TAG_FILL_TYPE 12
 #define MDX_TAG_FILL_VOXEL 13
+#define MDX_TAG_TRAIN_TIME_INDEX 14
+#define MDX_TAG_TRAIN_Z 15
+#define MDX_TAG_TRAIN_U 16
+#define MDX_TAG_TRAIN_LATTICE 17
 
 #if defined(__GNUC__)
 #define MDX_API __attribute__((visibility("default")))
@@ -281,6 +288,40 @@ MDX_API int mdx_noise_atom_types_per_atom(const int64_t* a0, const float* q_bar,
                                           int num_classes, int64_t* out, mdx_stream_t stream);
 MDX_API int mdx_noise_lattice_parameters(const float* l0, const float* z, const float* sigmas_n, int64_t count, float* out,
                                          mdx_stream_t stream);
+
+/* The training side's batch: NoisingTransform.transform (data/diffusion/noising_transform.py:82-200) of `batch` rows of a
+ * device-resident dataset in ONE launch -- the gather of the rows, a time index per structure, the schedule's rows there, F1, F2
+ * and F3 (the same device functions as the stand-alone entries above: the same bits).
+ * Dataset: x0 f32 [M,N,d], a0 int64 [M,N], l0 f32 [M,nl], nl = d(d+1)/2, M = dataset_size.  Structure b of the batch is row
+ *   r = rows ? rows[p] : p,   p = row_offset + cursor * batch + b,   cursor = d_cursor ? *d_cursor : 0
+ * rows (nullable) int64 [rows_count], e.g. an epoch's permutation; d_cursor (nullable) a device word, so that a launch captured
+ * into a hipGraph walks the permutation as the word is incremented; row_offset addresses a tail batch (batch = what is left).
+ * Time index: time_indices_in[b] (int64 [B]) or, NULL, from the device RNG: (w T) >> 32 of one 32-bit Philox word w, in 64-bit
+ * integer arithmetic -- in [0, T) by construction.  The rows of sched_host's time, sigma, q_matrix, q_bar_matrix and
+ * q_bar_tm1_matrix at that index are the structure's.
+ *   xt = wrap(x0[r] + sigma z)                                   (F1)
+ *   at = argmax_c(log Qbar[a0[r]][c] - log(-log u_c))            (F2, the first maximum)
+ *   lt = (sigma / root) z_l + l0[r]                              (F3; root = N^(1/d) as the caller's binary32 number)
+ *        use_fixed_lattice_parameters != 0: lt = l0[r], and no lattice draw is made
+ * Noise: z [B,N,d], u [B,N,C], z_lattice [B,nl] pre-drawn and indexed by the position in the BATCH; a NULL pointer switches that
+ * draw to the device RNG, keyed by the DATASET ROW: counter = (item, (call << 8) | k/4, rng.draw_offset, tag) with
+ *   MDX_TAG_TRAIN_TIME_INDEX  item = r, word 0           MDX_TAG_TRAIN_Z        item = r N + atom, k = the dimension
+ *   MDX_TAG_TRAIN_LATTICE     item = r, k = parameter    MDX_TAG_TRAIN_U        item = r N + atom, k = the class
+ * (what mdx_rng_fill writes at those items: kind 1 for z and z_lattice, kind 0 for u) and call = rng.call_dev ? *rng.call_dev :
+ * rng.call.  A row's noise therefore does not depend on the batch it sits in, its size or its order, and a fixed call
+ * reproduces a dataset noised once without storing it.  rng.draw_stride is not read.
+ * Outputs, every pointer nullable: x0_out [B,N,d], a0_out [B,N], l0_out [B,nl] (the gathered clean rows); time_indices_out int64
+ * [B], time_out [B], sigma_out [B]; xt_out, at_out, lt_out; q_out, q_bar_out, q_bar_tm1_out [B,C,C] (one row per structure).
+ * status (nullable): MDX_STATUS_NOISING_INDEX.  M N >= 2^32 (the 32-bit Philox item): MDX_ERR_INVALID_ARG.  d <= 3 and
+ * C <= MDX_MAX_CLASSES, else MDX_ERR_UNSUPPORTED. */
+MDX_API int mdx_noise_training_batch(const mdx_schedule_t* sched_host, const float* x0, const int64_t* a0, const float* l0,
+                                     int64_t dataset_size, const int64_t* rows, int64_t rows_count, int64_t row_offset,
+                                     const int32_t* d_cursor, const int64_t* time_indices_in, const float* z, const float* u,
+                                     const float* z_lattice, mdx_rng_t rng, int64_t batch, int number_of_atoms,
+                                     int spatial_dimension, float root, int use_fixed_lattice_parameters, float* x0_out,
+                                     int64_t* a0_out, float* l0_out, int64_t* time_indices_out, float* time_out, float* sigma_out,
+                                     float* xt_out, int64_t* at_out, float* lt_out, float* q_out, float* q_bar_out,
+                                     float* q_bar_tm1_out, uint32_t* status, mdx_stream_t stream);
 
 /* R1 -- ConstrainedLangevinGenerator._repaint_composition (generators/constrained_langevin_generator.py:136-163):
  * for each sample and each constrained row k: forward-noise the known (x_k, a_k) to time index `index_i`
